@@ -14,9 +14,11 @@ Besides the headline the default run also measures (same shape, same patients; S
                             (MFMA fraction), cpu_baseline and parity (oracle pipeline on a sample)
   * "dopri5_step"        -- BASELINE config 3 per GPU: adaptive solve + tape adjoint, with roofline (per attempt),
                             cpu_baseline and parity (the oracle's step algebra replayed along the run's own tape)
-`--headline-only` skips the two extra blocks, `--no-cpu` every CPU leg.
+`--headline-only` skips the two extra blocks, `--no-cpu` every CPU leg.  `--dump-outputs DIR` writes what the last timed
+step computed (rank 0: trajectory h and the adjoint's gradients) as float32 DIR/<name>.npy, for output-for-output
+comparison of two builds on the same seeded inputs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 `python bench.py --gpus N` without a launcher starts that command itself (before anything touches the GPU).
@@ -648,6 +650,34 @@ class Watchdog:
         return False
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, plan, flat, stub, theta_grad):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as float32 DIR/<name>.npy.
+    h (T, B, D) is the trajectory, grad_* the discrete adjoint's gradients for the fixed cotangent (the all-reduced bucket
+    when distributed).  The inputs are seeded (solver_problem), so two builds can be compared file for file."""
+    import numpy as np
+    import torch
+    if stub:
+        arrays = {"grad_flat": flat}
+    else:
+        n_w, n_b = plan.n_w, plan.n_b
+        arrays = {"h": plan.h, "grad_y0": plan.grad_y0, "grad_w": flat[:n_w].view(plan.grad_w.shape),
+                  "grad_b": flat[n_w:n_w + n_b]}
+        if theta_grad:
+            arrays["grad_theta"] = flat[n_w + n_b:]
+        torch.cuda.synchronize()
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    log("dumped %s to %s (%.1f MB)" % (", ".join("%s%s" % (k, list(a.shape)) for k, a in arrays.items()), dirname, total / 2**20))
+
+
 def supervise(args, modes):
     """Rank-level guard for N > 1 (runs in every process torch.distributed.run starts, BEFORE anything touches the GPU):
     start the real rank as a child with the first exchange mode; if it leaves with a non-zero code (GUARD_EXIT: its
@@ -737,7 +767,11 @@ def main():
     ap.add_argument("--no-tape", action="store_true", help="backward re-integrates the expert stages instead of reading the forward's tape")
     ap.add_argument("--full-step", action="store_true", help="(default now) kept for compatibility")
     ap.add_argument("--dopri5", action="store_true", help="(default now) kept for compatibility")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (trajectory, gradients) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.graph_allreduce:
         args.grad_exchange = "graph"
     if args.sync_allreduce:
@@ -856,6 +890,8 @@ def main():
     from hode.parallel import AlternatingExchange
     exchange = AlternatingExchange(lambda buf: avg(buf, async_op=True)) if overlap else None
 
+    last_bucket = [0]   # the gradient bucket the most recent step wrote (alternates on the overlap path)
+
     def step():
         if step_graph is not None:
             step_graph.replay()
@@ -864,6 +900,7 @@ def main():
             i = exchange.acquire()          # waits (stream-side) for the exchange issued two steps ago on this bucket
             plan.replay(i)                  # the graph captured for bucket i
             exchange.release(i, plan.buckets[i])
+            last_bucket[0] = i
             return
         if use_graph:
             plan.replay()
@@ -907,6 +944,9 @@ def main():
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, plan, plan.buckets[last_bucket[0]] if overlap else plan.grad_flat, stub,
+                     not args.no_theta_grad)
 
     extras = not args.headline_only and not stub
     cpu = not args.no_cpu and world == 1 and not stub

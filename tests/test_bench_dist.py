@@ -8,6 +8,9 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -72,3 +75,19 @@ def test_self_launch_without_a_launcher():
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     out = json.loads(lines[-1])
     assert out["n_gpus"] == 2 and "serialised" in out["config"]["grad_exchange"]
+
+
+@pytest.mark.parametrize("exchange", ["graph", "overlap"])
+def test_dump_outputs_writes_the_last_steps_all_reduced_bucket(tmp_path, exchange):
+    """--dump-outputs DIR: rank 0 writes what the last timed step left for its caller, float32 .npy (the stub's bucket:
+    every rank fills it with rank + 1, gloo sums -> 3)."""
+    out_dir = tmp_path / "dump"
+    r, lines = _run(_launcher(_free_port()) + ["--grad-exchange", exchange, "--dump-outputs", str(out_dir)], {})
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out["steps"] == 5 and out["ms_per_step"] > 0
+    assert sorted(os.listdir(out_dir)) == ["grad_flat.npy"]
+    g = np.load(out_dir / "grad_flat.npy")
+    assert g.dtype == np.float32 and g.shape == (120,)
+    assert (g == 3.0).all()

@@ -20,6 +20,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin/"
@@ -43,7 +44,11 @@ def kernel_ops(co, symbol):
     return ops
 
 
-def check(tpw, nt, flat=True, verbose=False, tmp="/tmp/hode_isa", obj=None):
+def check(tpw, nt, flat=True, verbose=False, tmp=None, obj=None):
+    """`tmp`: directory for the extracted code object; default a private temporary directory, removed afterwards."""
+    if tmp is None:
+        with tempfile.TemporaryDirectory(prefix="hode_isa_") as d:
+            return check(tpw, nt, flat=flat, verbose=verbose, tmp=d, obj=obj)
     obj = obj or os.path.join(ROOT, "hybrid-ode-neurips-2021_amd", "csrc", "build", "hode_lstm_tpw%d.o" % tpw)
     if not os.path.exists(obj):
         raise SystemExit("check_lstm_isa: %s not built (python build_hip.py)" % obj)

@@ -1,5 +1,6 @@
-import sys, torch
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/hybrid-ode-neurips-2021_amd'); sys.path.insert(0,'/root/repo/tests')
+import os, sys, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'hybrid-ode-neurips-2021_amd')); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import test_hip_dopri5 as T
 from oracle.solvers import odeint_dopri5_replay
 from oracle.rhs import THETA_NAMES
