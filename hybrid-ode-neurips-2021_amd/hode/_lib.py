@@ -113,6 +113,21 @@ class McKlDesc(C.Structure):
     ]
 
 
+SEQDEC_TLSTM, SEQDEC_GRUODE = 0, 1
+SEQDEC_MAX_LATENT = 29
+
+
+class SeqdecDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("kind", C.c_int32), ("n_steps", C.c_int32), ("n_action_times", C.c_int32),
+        ("batch", C.c_int32), ("latent_dim", C.c_int32), ("action_dim", C.c_int32), ("reserved", C.c_int32),
+        ("step_index", _fp), ("step_time", _fp), ("a", _fp), ("init", _fp), ("w0", _fp), ("w1", _fp), ("b0", _fp),
+        ("b1", _fp), ("h", _fp), ("c", _fp), ("grad_h", _fp), ("grad_init", _fp), ("grad_w0", _fp), ("grad_w1", _fp),
+        ("grad_b0", _fp), ("grad_b1", _fp),
+        ("workspace", _fp), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 #: every symbol include/hode.h declares: (name, restype, argtypes)
 EXPORTS = (
     ("hode_version", C.c_int, ()),
@@ -134,6 +149,9 @@ EXPORTS = (
     ("hode_lstm_fwd", C.c_int, (C.POINTER(LstmDesc), C.c_void_p)),
     ("hode_lstm_bwd", C.c_int, (C.POINTER(LstmDesc), C.c_void_p)),
     ("hode_lstm_fill_operand", C.c_int, (C.POINTER(LstmDesc), C.c_void_p)),
+    ("hode_seqdec_workspace_bytes", C.c_size_t, (C.POINTER(SeqdecDesc),)),
+    ("hode_seqdec_fwd", C.c_int, (C.POINTER(SeqdecDesc), C.c_void_p)),
+    ("hode_seqdec_bwd", C.c_int, (C.POINTER(SeqdecDesc), C.c_void_p)),
 )
 
 _lib = None

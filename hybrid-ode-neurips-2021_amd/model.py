@@ -12,8 +12,9 @@ latent ODE is integrated by the gfx950 kernels of ``libhode.so`` (``hode.odeint`
     VariationalInference model.py:1124-1214    VariationalInference
 
     EncoderLSTMReal / RocheODEReal / DecoderReal / VariationalInferenceReal  model.py:180-242, 570-657, 772-862, 1217-1261
+    GRUODECell / DecoderRealBenchmark ("tlstm", "gruode" baselines)         model.py:865-966  (hode.seqdec kernels)
 
-Out of scope: flow encoders, baselines (NeuralODEReal*, DecoderRealBenchmark).
+Out of scope: flow encoders, the NeuralODEReal* baselines.
 """
 
 from __future__ import annotations
@@ -577,6 +578,103 @@ class DecoderReal(nn.Module):
         from hode import readout
         l0, l2 = self.output_function[0], self.output_function[2]
         return readout.masked_sse_readout_mlp(h, x, mask, l0.weight, l0.bias, l2.weight, l2.bias, time_weight, skip_rows=1)
+
+
+class GRUODECell(nn.Module):
+    """GRU-ODE cell of the ``gruode`` baseline (reference model.py:865-886).  ``forward(a, h_all)`` is the eager arithmetic:
+    with x = [h_all[0], a], z = sigmoid(lin_hz x) and n = tanh(lin_hn(z * x)) it returns (1 - z[..., :D]) * (n - h_all[0])
+    together with the state it was handed, (h_all[0], 0).  ``DecoderRealBenchmark`` runs the same cell in one kernel."""
+
+    def __init__(self, hidden_size, bias=True):
+        super().__init__()
+        self.hidden_size = hidden_size
+        self.lin_hz = nn.Linear(hidden_size + 2, hidden_size + 2, bias=False)
+        self.lin_hn = nn.Linear(hidden_size + 2, hidden_size, bias=False)
+
+    def forward(self, a, h_all):
+        state = h_all[0]
+        x = torch.cat([state, a], dim=-1)
+        z = torch.sigmoid(self.lin_hz(x))
+        n = torch.tanh(self.lin_hn(z * x))
+        return (1 - z[:, :, : self.hidden_size]) * (n - state), (state, 0)
+
+
+class DecoderRealBenchmark(nn.Module):
+    """Recurrent baselines of the real-data experiment (reference model.py:889-966): z0 -> h over t = t0 .. t_max - 1 ->
+    MLP readout; unlike ``DecoderReal`` no output row is dropped.
+
+    ``tlstm``: nn.LSTM(2 action_dim, D) stepped over the grid with h0 = c0 = init, input [a[t], t / t_max].
+    ``gruode``: the reference hands ``GRUODECell`` the pair (hidden, c) and takes back (out, (hidden, c)); the cell returns
+    the state it was given, so the hidden state stays ``init`` at every step and h[k] is the cell's output for
+    x_k = [init, a[t_k], t_k / t_max].  That is what the published numbers ran; it is reproduced, not fixed.
+
+    Both run as one gfx950 kernel per direction (``hode.seqdec``); CPU tensors raise ``HodeConfigError``.  ``method``,
+    ``ode_step_size`` and ``hidden_dim`` are stored and unused, as in the reference.  The cell is moved to ``device`` with
+    the rest of the module (the reference leaves it on the default device)."""
+
+    def __init__(self, obs_dim, latent_dim, action_dim, static_dim, hidden_dim, t_max, step_size, t0=0, method="dopri5",
+                 ode_step_size=None, ode_type="tlstm", device=None, dtype=DTYPE):
+        super().__init__()
+        self.time_dim = int(t_max / step_size)
+        self.obs_dim, self.latent_dim, self.action_dim = obs_dim, latent_dim, action_dim
+        self.t_max, self.t0, self.step_size = t_max, t0, step_size
+        self.static_dim, self.hidden_dim = int(static_dim), int(hidden_dim)
+        self.model_name = "DecoderReal_" + ode_type
+        self.device = get_device() if device is None else device
+        # readout first, then the cell: the reference's parameter creation order (seeded-init parity)
+        self.output_function = nn.Sequential(nn.Linear(latent_dim, latent_dim + 1, bias=True), nn.ELU(),
+                                             nn.Linear(latent_dim + 1, obs_dim, bias=True)).to(self.device)
+        self.ode_type = ode_type
+        if ode_type == "tlstm":
+            self.rnn = nn.LSTM(action_dim * 2, latent_dim).to(self.device)
+        elif ode_type == "gruode":
+            self.rnn = GRUODECell(latent_dim).to(self.device)
+        else:
+            raise hode.HodeConfigError("DecoderRealBenchmark(ode_type=%r): the baselines are 'tlstm' and 'gruode'" % (ode_type,))
+        self.t = torch.arange(t0, t_max, step_size, device=self.device, dtype=dtype)
+        self.method = method
+        self.step_size = ode_step_size
+        self._tables = None
+
+    def _step_tables(self, device):
+        """Action row and time feature of every step, built once per grid tensor and device (one host read-back)."""
+        key = (self.t, self.t._version, self.t_max, device)
+        if self._tables is None or self._tables[0] is not key[0] or self._tables[1:4] != key[1:]:
+            from hode import seqdec
+            self._tables = key + seqdec.step_tables(self.t, self.t_max, device)
+        return self._tables[4:]
+
+    def latent(self, init, a, s):
+        """Decoder outputs h (len(t), B, D) before the readout."""
+        from hode import seqdec
+        from hode.solver import _require_gpu
+        _require_gpu(init, a)
+        if init.dim() != 2:
+            raise hode.HodeConfigError("DecoderRealBenchmark: per-step initial states (3-D init) are outside the accelerated path")
+        idx, tau, max_row = self._step_tables(init.device)
+        if self.ode_type == "tlstm":
+            r = self.rnn
+            return seqdec.tlstm(init, a, idx, tau, max_row, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)
+        return seqdec.gruode(init, a, idx, tau, max_row, self.rnn.lin_hz.weight, self.rnn.lin_hn.weight)
+
+    def forward(self, init, a, s):
+        h = self.latent(init, a, s)
+        if h.shape[0] * h.shape[1] >= 65536:
+            return _tall_mlp(self.output_function, h), h
+        return self.output_function(h), h
+
+    def fused_likelihood_ok(self, x):
+        from hode import readout
+        return x.is_cuda and readout.mlp_supported(self.latent_dim, self.output_function[0].out_features, self.obs_dim)
+
+    def masked_sse(self, h, x, mask, time_weight=None):
+        """sum((x - output_function(h))^2 * mask * time_weight) / B in one fused pass over the rows (every row of h)."""
+        from hode import readout
+        if h.shape[0] != x.shape[0] or h.shape[1] != x.shape[1]:
+            raise hode.HodeConfigError("DecoderRealBenchmark.masked_sse: h has %d x %d rows, x %d x %d" % (h.shape[0], h.shape[1],
+                                                                                                        x.shape[0], x.shape[1]))
+        l0, l2 = self.output_function[0], self.output_function[2]
+        return readout.masked_sse_readout_mlp(h, x, mask, l0.weight, l0.bias, l2.weight, l2.bias, time_weight, skip_rows=0)
 
 
 class VariationalInference:

@@ -278,6 +278,49 @@ typedef struct hode_mckl_desc {
   float* grad_log_var;   /* out [rows] d kl[i] / d log_var[i], or NULL */
 } hode_mckl_desc;
 
+/* Real-data recurrent baseline decoders (reference DecoderRealBenchmark, model.py:889-966), one launch per direction.
+ *   HODE_SEQDEC_TLSTM : nn.LSTM(2 action_dim, D) stepped over k = 0 .. T'-1 with h0 = c0 = init; h[k] = hidden state
+ *                       after step k.  w0 = weight_ih [4D][2], w1 = weight_hh [4D][D], b0 = bias_ih [4D], b1 = bias_hh [4D].
+ *   HODE_SEQDEC_GRUODE: GRUODECell(D) as the reference calls it: the hidden state handed to the cell is `init` at every
+ *                       step, h[k] = (1 - z[:D]) (tanh(w1 (z x_k)) - init), z = sigmoid(w0 x_k), x_k = [init, a, tau]
+ *                       (no recurrence).  w0 = lin_hz.weight [D+2][D+2], w1 = lin_hn.weight [D][D+2]; b0 / b1 unused.
+ * Step k reads a[step_index[k]][b] and the time feature step_time[k], both tables built by the caller as the reference
+ * forms them (t = int(t_k), tau = fp32(t) / t_max).  latent_dim 1 .. HODE_SEQDEC_MAX_LATENT, action_dim 1.
+ * The backward overwrites grad_init and the weight gradients (grad_b0 and grad_b1 both receive the bias gradient); it
+ * folds one partial block per wave in a fixed order (no float atomics) and needs hode_seqdec_workspace_bytes of workspace. */
+#define HODE_SEQDEC_TLSTM 0
+#define HODE_SEQDEC_GRUODE 1
+#define HODE_SEQDEC_MAX_LATENT 29 /* [h, a, tau, 1] fits two 16-row tiles */
+
+typedef struct hode_seqdec_desc {
+  uint32_t struct_size;
+  int32_t kind;               /* HODE_SEQDEC_* */
+  int32_t n_steps;            /* T' */
+  int32_t n_action_times;     /* Ta: rows of a (step_index values are clamped into [0, Ta)) */
+  int32_t batch;              /* B */
+  int32_t latent_dim;         /* D */
+  int32_t action_dim;         /* 1 */
+  int32_t reserved;
+  const int32_t* step_index;  /* [T'] */
+  const float* step_time;     /* [T'] */
+  const float* a;             /* [Ta][B][action_dim] */
+  const float* init;          /* [B][D] */
+  const float* w0;
+  const float* w1;
+  const float* b0;
+  const float* b1;
+  float* h;                   /* [T'][B][D]: out of the forward, read by the tlstm backward */
+  float* c;                   /* tlstm: [T'][B][D] cell-state tape, written by the forward if non-NULL, read by the backward */
+  const float* grad_h;        /* backward: [T'][B][D] */
+  float* grad_init;           /* backward out: [B][D] */
+  float* grad_w0;             /* backward out, shaped like w0 */
+  float* grad_w1;             /* backward out, shaped like w1 */
+  float* grad_b0;             /* tlstm backward out [4D] */
+  float* grad_b1;             /* tlstm backward out [4D] */
+  void* workspace;            /* backward: >= hode_seqdec_workspace_bytes */
+  size_t workspace_bytes;
+} hode_seqdec_desc;
+
 #define HODE_WS_RK_FWD 0
 #define HODE_WS_RK_BWD 1
 #define HODE_WS_DOPRI5_FWD 2
@@ -345,6 +388,10 @@ int hode_lstm_bwd(const hode_lstm_desc* desc, void* hip_stream);
  * the product that reads h_prev.  Takes the descriptor of the hode_lstm_bwd call it belongs to (validated as a whole); reads
  * seq_len, batch, input_dim, hidden_dim, obs_dim, x, mask and writes h_prev. */
 int hode_lstm_fill_operand(const hode_lstm_desc* desc, void* hip_stream);
+
+size_t hode_seqdec_workspace_bytes(const hode_seqdec_desc* desc);
+int hode_seqdec_fwd(const hode_seqdec_desc* desc, void* hip_stream);
+int hode_seqdec_bwd(const hode_seqdec_desc* desc, void* hip_stream);
 
 #ifdef __cplusplus
 }
