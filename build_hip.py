@@ -34,7 +34,7 @@ def units():
         u.append(("hode_dp_d%d" % d, os.path.join(CSRC, "hode_dopri5_dim.hip"), ["-DHODE_DIM=%d" % d] + DP_FLAGS))
     for n in LSTM_TPWS:
         u.append(("hode_lstm_tpw%d" % n, os.path.join(CSRC, "hode_lstm_tpw.hip"), ["-DHODE_LSTM_TPW=%d" % n] + EXTRA_FLAGS["hode_lstm"]))
-    for name in ("hode_dopri5", "hode_lstm", "hode_neural", "hode_real", "hode_rk_mf", "hode_readout", "hode_rk_split", "hode_crps", "hode_mckl", "hode_neural_mf", "hode_real_mf", "hode_neural_dopri5", "hode_readout_mlp", "hode_seqdec"):
+    for name in ("hode_dopri5", "hode_lstm", "hode_neural", "hode_real", "hode_rk_mf", "hode_readout", "hode_rk_split", "hode_crps", "hode_mckl", "hode_neural_mf", "hode_real_mf", "hode_neural_dopri5", "hode_readout_mlp", "hode_seqdec", "hode_neural_real_mf"):
         src = os.path.join(CSRC, name + ".hip")
         if os.path.exists(src):
             u.append((name, src, EXTRA_FLAGS.get(name, [])))

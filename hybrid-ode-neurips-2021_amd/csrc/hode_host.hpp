@@ -67,6 +67,10 @@ bool real_mf_supported(const hode_solve_desc* d);                               
 int launch_real_mf(const hode_solve_desc* d, const RealArgs& a, bool bwd, hipStream_t s);
 size_t real_mf_partial_bytes(const hode_solve_desc* d);
 
+// real-data neural ODE baselines (hode_neural_real_mf.hip)
+size_t neural_real_workspace_bytes(const hode_solve_desc* d, bool bwd);
+int neural_real_rk(const hode_solve_desc* d, bool bwd, hipStream_t s);
+
 // MFMA-layout Roche kernels (hode_rk_mf.hip)
 bool mf_supported(const hode_solve_desc* d);
 size_t mf_workspace_bytes(const hode_solve_desc* d);

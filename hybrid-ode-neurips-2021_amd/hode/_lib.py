@@ -11,6 +11,7 @@ _LIB_NAME = "libhode.so"
 HODE_ABI_VERSION = 1
 
 RHS_ROCHE, RHS_ROCHE_ABLATE, RHS_NEURAL, RHS_ROCHE_REAL = 0, 1, 2, 3
+RHS_NEURAL_REAL, RHS_NEURAL_REAL_2ND = 4, 5
 METHOD_EULER, METHOD_MIDPOINT, METHOD_RK4_38 = 0, 1, 2
 METHODS = {"euler": METHOD_EULER, "midpoint": METHOD_MIDPOINT, "rk4": METHOD_RK4_38}
 N_THETA = 16

@@ -13,8 +13,9 @@ latent ODE is integrated by the gfx950 kernels of ``libhode.so`` (``hode.odeint`
 
     EncoderLSTMReal / RocheODEReal / DecoderReal / VariationalInferenceReal  model.py:180-242, 570-657, 772-862, 1217-1261
     GRUODECell / DecoderRealBenchmark ("tlstm", "gruode" baselines)         model.py:865-966  (hode.seqdec kernels)
+    NeuralODEReal / NeuralODEReal2nd ("neural", "2nd" baselines)           model.py:660-769  (hode.neural_real kernels)
 
-Out of scope: flow encoders, the NeuralODEReal* baselines.
+Out of scope: flow encoders.
 """
 
 from __future__ import annotations
@@ -460,6 +461,101 @@ class RocheODEReal(nn.Module):
             t, step_size)
 
 
+class _NeuralODERealBase(nn.Module):
+    """Shared body of the neural ODE baselines of the real-data experiment (reference model.py:660-769): an MLP on
+    [y, dose(t)] with dose(t) = cumsum(action, 0)[int(t)] (zeros once int(t) >= Ta).  ``forward`` is the reference's eager
+    rhs; ``hode_solve`` integrates on the gfx950 kernels (``hode.neural_real``), which run on a HIP device only."""
+
+    kind = None
+
+    def __init__(self, latent_dim, action_dim, static_dim, hidden_dim, t_max, step_size, out_dim, device=None, dtype=DTYPE):
+        super().__init__()
+        self.action_dim, self.latent_dim = int(action_dim), int(latent_dim)
+        self.static_dim, self.hidden_dim = int(static_dim), int(hidden_dim)
+        self.device = get_device() if device is None else device
+        self.t_max, self.step_size = t_max, step_size
+        self.ml_net = nn.Sequential(nn.Linear(self.latent_dim + self.action_dim, self.hidden_dim), nn.Tanh(),
+                                    nn.Linear(self.hidden_dim, out_dim), nn.Tanh()).to(self.device)
+        self.action = None
+        self.static = None
+        self._rows = None
+
+    def set_action_static(self, action, static):
+        self.action = action
+        self.static = static[0, :, :] if static is not None and static.dim() == 3 else static  # stored, unused
+
+    def dose_at_time(self, t):
+        t_int = int(t)
+        if t_int >= self.action.shape[0]:
+            return torch.zeros_like(self.action[0, :, :])
+        return torch.cumsum(self.action, dim=0)[t_int, :, :]
+
+    def _table_index(self, grid, method, perturb, device):
+        """Flat dose-table rows of every (interval, stage) of the solve over ``grid``: one host read-back per grid tensor
+        (cached on its identity and version, like DecoderRealBenchmark's step tables), so a training step has no sync."""
+        from hode import neural_real
+        Ta = int(self.action.shape[0])
+        key = (grid, grid._version, method, bool(perturb), Ta, device)
+        if self._rows is None or self._rows[0] is not grid or self._rows[1:6] != key[1:]:
+            rows = neural_real.stage_rows(grid, method, perturb, Ta)
+            self._rows = key + (neural_real.table_index(rows, Ta).reshape(-1).to(device),)
+        return self._rows[6]
+
+    def hode_solve(self, y0, t, rtol, atol, method, options):
+        from hode import neural_real, substep
+        neural_real.check_config(self.kind, self.latent_dim, self.hidden_dim, self.action_dim, method)
+        if self.action is None:
+            raise RuntimeError("%s: call set_action_static(a, s) before integrating" % type(self).__name__)
+        step_size = options.pop("step_size", None)
+        if step_size is not None and t.numel() > 1:
+            # the solver grid t0 + k*step_size IS the output grid at run_real.py's default (ode_step_div = 1): nothing to
+            # interpolate (the check is a host read-back, cached per grid tensor as in RocheODEReal)
+            cache = getattr(self, "_uniform_grid_cache", None)
+            if cache is None or cache[0] is not t or cache[1] != (t._version, float(step_size)):
+                cache = (t, (t._version, float(step_size)), bool(torch.allclose(t[1:] - t[:-1], torch.full_like(t[1:], float(step_size)))))
+                self._uniform_grid_cache = cache
+            if cache[2]:
+                step_size = None
+        options.pop("step_t", None)  # ignored by fixed-grid solvers (torchdiffeq only warns)
+        perturb = bool(options.pop("perturb", False))
+        l0, l2 = self.ml_net[0], self.ml_net[2]
+
+        def solve_on(grid):
+            index = self._table_index(grid, method, perturb, y0.device)
+            return neural_real.neural_real_solve(self.kind, y0, l0.weight, l0.bias, l2.weight, l2.bias, grid, self.action,
+                                                 index, method)
+
+        return substep.solve_with_step_size(solve_on, t, step_size)
+
+
+class NeuralODEReal(_NeuralODERealBase):
+    """``neural`` baseline (reference model.py:710-769): dy/dt = ml_net([y, dose(t)]), ml_net = Linear(D+1, H), Tanh,
+    Linear(H, D), Tanh."""
+
+    kind = "neural"
+
+    def __init__(self, latent_dim, action_dim, static_dim, hidden_dim, t_max, step_size, device=None, dtype=DTYPE):
+        super().__init__(latent_dim, action_dim, static_dim, hidden_dim, t_max, step_size, int(latent_dim), device, dtype)
+
+    def forward(self, t, y):
+        dose = self.dose_at_time(t)
+        return self.ml_net(torch.cat([y, dose], dim=-1))
+
+
+class NeuralODEReal2nd(_NeuralODERealBase):
+    """``2nd`` baseline (reference model.py:660-707): dy/dt = [ml_net([y, dose(t)]), y[:, :D//2]], ml_net = Linear(D+1, H),
+    Tanh, Linear(H, D//2), Tanh.  Odd D cannot be integrated (the derivative has D - 1 columns); ``hode_solve`` refuses it."""
+
+    kind = "2nd"
+
+    def __init__(self, latent_dim, action_dim, static_dim, hidden_dim, t_max, step_size, device=None, dtype=DTYPE):
+        super().__init__(latent_dim, action_dim, static_dim, hidden_dim, t_max, step_size, int(latent_dim) // 2, device, dtype)
+
+    def forward(self, t, y):
+        dose = self.dose_at_time(t)
+        return torch.cat([self.ml_net(torch.cat([y, dose], dim=-1)), y[..., : (self.latent_dim // 2)]], dim=-1)
+
+
 class _TallLinear(torch.autograd.Function):
     """``x @ W.T + b`` for x with ~1e6 rows and ~20 columns.  Same numbers as ``nn.Linear``; the backward forms the bias
     gradient as a (1 x rows) GEMM -- torch's column sum over such a shape takes 2 ms at 0.8 M x 21 (config 5), two orders
@@ -528,7 +624,9 @@ def _tall_mlp(seq, x):
 
 
 class DecoderReal(nn.Module):
-    """z0 -> h over t = t0-1 .. t_max-1 -> MLP readout, first output row dropped (model.py:772-862; hybrid ode_type)."""
+    """z0 -> h over t = t0-1 .. t_max-1 -> MLP readout, first output row dropped (model.py:772-862).  ``ode_type``
+    "neural" / "2nd" build the neural ODE baselines (``NeuralODEReal`` / ``NeuralODEReal2nd``), which run on the GPU
+    kernels only: constructing them on a non-HIP device raises ``HodeConfigError``; anything else is the hybrid rhs."""
 
     def __init__(self, obs_dim, latent_dim, action_dim, static_dim, hidden_dim, t_max, step_size, t0=0, method="dopri5",
                  ode_step_size=None, ode_type="neural", device=None, dtype=DTYPE):
@@ -542,8 +640,15 @@ class DecoderReal(nn.Module):
         self.output_function = nn.Sequential(nn.Linear(latent_dim, latent_dim + 1, bias=True), nn.ELU(),
                                              nn.Linear(latent_dim + 1, obs_dim, bias=True)).to(self.device)
         if ode_type in ("neural", "2nd"):
-            raise hode.HodeConfigError("DecoderReal(ode_type=%r): NeuralODEReal baselines are outside the accelerated path" % ode_type)
-        self.ode = RocheODEReal(latent_dim, action_dim, static_dim, hidden_dim, t_max, step_size, self.device)
+            from hode import neural_real
+            neural_real.check_config(ode_type, latent_dim, hidden_dim, action_dim)
+            if torch.device(self.device).type != "cuda":
+                raise hode.HodeConfigError("DecoderReal(ode_type=%r): the NeuralODEReal baselines run on the GPU kernels only "
+                                           "(device %s)" % (ode_type, self.device))
+            cls = NeuralODEReal if ode_type == "neural" else NeuralODEReal2nd
+            self.ode = cls(latent_dim, action_dim, static_dim, hidden_dim, t_max, step_size, self.device)
+        else:
+            self.ode = RocheODEReal(latent_dim, action_dim, static_dim, hidden_dim, t_max, step_size, self.device)
         self.t = torch.arange(t0 - 1, t_max, step_size, device=self.device, dtype=dtype)
         self.options = {"step_t": self.t, "step_size": ode_step_size, "perturb": True}
         self.rtol, self.atol = 1e-7, 1e-8

@@ -8,6 +8,7 @@
  *       func = RocheODE.forward      model.py:515-555   (HODE_RHS_ROCHE / HODE_RHS_ROCHE_ABLATE)
  *       func = NeuralODE.forward     model.py:1019-1026 (HODE_RHS_NEURAL)
  *       func = RocheODEReal.forward  model.py:613-645   (HODE_RHS_ROCHE_REAL)
+ *       func = NeuralODEReal.forward / NeuralODEReal2nd.forward  model.py:660-769  (HODE_RHS_NEURAL_REAL / _2ND)
  *     -> hode_rk_fwd / hode_rk_bwd          (method in {"euler","midpoint","rk4"})
  *     -> hode_dopri5_fwd / hode_dopri5_bwd  (method "dopri5", the reference default, sim_config.py:50)
  *     The backward entry points replace autograd's replay of the solver ops triggered by
@@ -48,6 +49,8 @@ extern "C" {
 #define HODE_RHS_ROCHE_ABLATE 1 /* linear-oscillator expert block (ablate=True) model.py:545-549 */
 #define HODE_RHS_NEURAL 2       /* tanh(W2 tanh(W1 [y,Dose] + b1) + b2)          model.py:1019-1026 */
 #define HODE_RHS_ROCHE_REAL 3   /* two small MLPs + GRU-ODE block                model.py:613-645 */
+#define HODE_RHS_NEURAL_REAL 4  /* m([y, dose]), m = tanh(W2 tanh(W1 . + b1) + b2)  model.py:710-769 */
+#define HODE_RHS_NEURAL_REAL_2ND 5 /* [m([y, dose]), y[:D/2]]                    model.py:660-707 */
 
 /* fixed-grid methods (torchdiffeq names "euler", "midpoint", "rk4" = 3/8 rule) */
 #define HODE_METHOD_EULER 0
@@ -341,6 +344,17 @@ int hode_neural_tape_offsets(const hode_solve_desc* desc, size_t* out4);
 /* HODE_RHS_ROCHE_REAL backward: hode_rk_bwd fills grad_y0 and grad_theta[0..2] (k_immunity, kel, kel2) and tapes the
  * weight-gradient GEMM operands at the start of the workspace as tape[inst][rows][B], inst = (T-1)*stages,
  * rows = 5 + 4H + 5(D-4) in the order Y3(3) A11(H) U11(H) U12(1) A21(H) U21(H) U22(1) HH RH UR UZ UH (D-4 each). */
+
+/* HODE_RHS_NEURAL_REAL / HODE_RHS_NEURAL_REAL_2ND (hode_rk_fwd / hode_rk_bwd; workspace only for the backward).
+ * m has input D + 1 ([y, dose]), hidden H = hidden_dim and output Dm = D (NEURAL_REAL) or D / 2 (_2ND).  Fields read:
+ * method, batch, latent_dim (NEURAL_REAL 1..30; _2ND even 2..60), n_times (>= 1), hidden_dim (1..64), t [T] (only the
+ * step sizes t[n+1] - t[n] are used), y0 [B][D], w1 = ml_net.0.weight [H][D+1], b1 [H], w2 = ml_net.2.weight [Dm][H],
+ * b2 [Dm], h [T][B][D], and dosage = the dose input of every (interval, stage) as a table [T-1][stages][B] (NULL allowed
+ * when T == 1): the caller gathers it from cumsum(action) at the rows int(stage time) -- zero for rows >= Ta --, so
+ * `perturb` and the stage times never reach the device.  Backward: grad_h, grad_y0 (out), grad_w1 / grad_b1 / grad_w2 /
+ * grad_b2 (accumulators, each may be NULL), workspace.  The weight gradients are accumulated on chip, one partial block
+ * per wave, folded in a fixed order (bit-reproducible).  n_dose, dose_times, theta, n_action_times, lanes_per_patient,
+ * need_theta_grad and perturb are ignored; HODE_FLAG_OVERWRITE_GRADS / HODE_FLAG_SKIP_FOLD are HODE_E_UNSUPPORTED. */
 
 /* bytes of device scratch the given entry point needs for this descriptor (0 if none) */
 size_t hode_workspace_bytes(const hode_solve_desc* desc, int which);
