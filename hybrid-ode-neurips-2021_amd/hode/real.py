@@ -51,14 +51,13 @@ class _RealFixedGrid(torch.autograd.Function):
         method, perturb, H = ctx.meta
         lib = L.lib()
         T, B, D = h.shape
-        M = D - 4
         gh = grad_h.to(torch.float32).contiguous()
         gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)
         gth = torch.zeros(L.N_THETA, device=h.device, dtype=torch.float32)
         d = _desc(h[0], tc, ac, thc, wc, h, method, perturb, H)
         d.grad_h, d.grad_y0, d.grad_theta = gh.data_ptr(), gy0.data_ptr(), gth.data_ptr()
         # matrix-core kernels (D = 20, hidden <= 64): the weight gradients are accumulated on chip into this flat buffer;
-        # the lane-per-patient kernels (HODE_REAL_LAYOUT=t, D = 4) tape the GEMM operands for the contractions below
+        # the lane-per-patient kernels (HODE_REAL_LAYOUT=t, D = 4) tape the GEMM operands for contract_tape
         onchip = D == 20 and H <= 64 and os.environ.get("HODE_REAL_LAYOUT", "")[:1] != "t"
         if onchip:
             gw = torch.zeros_like(wc)
@@ -70,40 +69,48 @@ class _RealFixedGrid(torch.autograd.Function):
             L.check(lib.hode_rk_bwd(d, _stream()), "hode_rk_bwd[real]")
         if onchip:
             return gy0, gth[:3].clone(), gw, None, None, None, None, None
-        inst = (T - 1) * _STAGES[method]
-        rows = 5 + 4 * H + 5 * M
-        if inst == 0:
-            return gy0, gth[:3].clone(), torch.zeros_like(wc), None, None, None, None, None
-        tape = ws[: inst * rows * B * 4].view(torch.float32).view(inst, rows, B)
-        o = 0
+        return gy0, gth[:3].clone(), contract_tape(ws, T, B, D, H, method), None, None, None, None, None
 
-        def take(k):
-            nonlocal o
-            v = tape[:, o:o + k]
-            o += k
-            return v
 
-        y3, a11, u11, u12, a21, u21, u22 = take(3), take(H), take(H), take(1), take(H), take(H), take(1)
-        hh, rh, ur, uz, uh = (take(M) for _ in range(5)) if M > 0 else (None,) * 5
+def contract_tape(ws, T, B, D, H, method):
+    """Flat weight gradient (creation order of the flat weight buffer) from the GEMM operands a tape-writing backward left
+    at offset 0 of its workspace ``ws``: per stage instance, rows [y3 | a11 | u11 | u12 | a21 | u21 | u22 | hh rh ur uz uh]
+    of ``B`` floats each (the lane-per-patient kernels, and the matrix-core backward when the caller passes no grad_w1)."""
+    M = D - 4
+    inst = (T - 1) * _STAGES[method]
+    rows = 5 + 4 * H + 5 * M
+    if inst == 0:
+        return torch.zeros(9 * H + 2 + 3 * M * M, device=ws.device, dtype=torch.float32)
+    tape = ws[: inst * rows * B * 4].view(torch.float32).view(inst, rows, B)
+    o = 0
 
-        # sums over instances are (1 x inst) GEMMs: torch's strided sum over these shapes runs at a fraction of HBM speed
-        ones_i = torch.ones((1, inst), device=h.device, dtype=torch.float32)
-        ones_b = torch.ones((B, 1), device=h.device, dtype=torch.float32)
+    def take(k):
+        nonlocal o
+        v = tape[:, o:o + k]
+        o += k
+        return v
 
-        def fold(part):  # (inst, m, n) -> (m, n)
-            return (ones_i @ part.reshape(inst, -1)).view(part.shape[1], part.shape[2])
+    y3, a11, u11, u12, a21, u21, u22 = take(3), take(H), take(H), take(1), take(H), take(H), take(1)
+    hh, rh, ur, uz, uh = (take(M) for _ in range(5)) if M > 0 else (None,) * 5
 
-        def outer(u, x):  # sum over instances and patients of u x^T
-            return fold(torch.bmm(u, x.transpose(1, 2)))
+    # sums over instances are (1 x inst) GEMMs: torch's strided sum over these shapes runs at a fraction of HBM speed
+    ones_i = torch.ones((1, inst), device=ws.device, dtype=torch.float32)
+    ones_b = torch.ones((B, 1), device=ws.device, dtype=torch.float32)
 
-        def colsum(u):   # (inst, k, B) -> (k,)
-            return fold(u @ ones_b).reshape(-1)
+    def fold(part):  # (inst, m, n) -> (m, n)
+        return (ones_i @ part.reshape(inst, -1)).view(part.shape[1], part.shape[2])
 
-        parts = [outer(u11, y3).reshape(-1), colsum(u11), outer(u12, a11).reshape(-1), colsum(u12),
-                 outer(u21, y3[:, :2]).reshape(-1), colsum(u21), outer(u22, a21).reshape(-1), colsum(u22)]
-        if M > 0:
-            parts += [outer(uh, rh).reshape(-1), outer(uz, hh).reshape(-1), outer(ur, hh).reshape(-1)]
-        return gy0, gth[:3].clone(), torch.cat(parts), None, None, None, None, None
+    def outer(u, x):  # sum over instances and patients of u x^T
+        return fold(torch.bmm(u, x.transpose(1, 2)))
+
+    def colsum(u):   # (inst, k, B) -> (k,)
+        return fold(u @ ones_b).reshape(-1)
+
+    parts = [outer(u11, y3).reshape(-1), colsum(u11), outer(u12, a11).reshape(-1), colsum(u12),
+             outer(u21, y3[:, :2]).reshape(-1), colsum(u21), outer(u22, a21).reshape(-1), colsum(u22)]
+    if M > 0:
+        parts += [outer(uh, rh).reshape(-1), outer(uz, hh).reshape(-1), outer(ur, hh).reshape(-1)]
+    return torch.cat(parts)
 
 
 def real_solve(y0, theta, wflat, t, act, hidden, method="midpoint", perturb=True):
