@@ -10,7 +10,9 @@ namespace hode {
 constexpr int kWave = 64;
 
 // ---------------------------------------------------------------------------------------------------------
-// transcendental helpers.  Accuracy targets are stated per function and checked in tests/test_hip_math.py.
+// transcendental helpers.  Accuracy targets are stated per function.  No test checks these helpers on their own; they are
+// checked only through the kernels that use them, against float64 (tests/test_hip_kernel_variants.py: log_f32 and powf
+// through the Roche kernels' general-Hill body).
 // ---------------------------------------------------------------------------------------------------------
 
 // exp(x), x <= 0 in practice (dose decay kel*(tau - t)): hardware exp2 of the rounded product x*log2(e), corrected
@@ -27,7 +29,7 @@ HODE_DEV float exp_f32(float x) {
 HODE_DEV float log_f32(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
 
 // tanh(x) = 1 - 2 / (exp(2x) + 1): v_mul, v_exp, v_add, v_rcp, v_fma.  ABSOLUTE error <= 1.5e-7 over the whole
-// line (checked against fp64 in tests/test_hip_math.py); the relative error grows for |x| << 1, which does not
+// line (a design target, not measured by a direct test); the relative error grows for |x| << 1, which does not
 // matter here because tanh feeds an additive rate dy/dt.  NaN propagates, +-inf -> +-1.
 HODE_DEV float tanh_f32(float x) {
   const float e = __builtin_amdgcn_exp2f(x * 2.885390081777927f);  // exp(2x)

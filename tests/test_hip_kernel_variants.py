@@ -9,7 +9,10 @@ rel-L2 1e-4 (2e-4 for the real-data neural ODEs).
 
 need_theta=False (theta not a leaf: frozen expert parameters, bench.py's inputs) selects its own backward instantiations;
 their grad_y0 / grad_w / grad_b are checked against fp64 and against the same call with need_theta=True (_same_as_with_theta):
-the theta accumulation is separate work that feeds nothing else."""
+the theta accumulation is separate work that feeds nothing else.
+
+The Roche and dopri5 cases also name the rhs body each kernel runs (kv.body): the theta vector and the number of dose times
+per patient are part of the problem, and grad_theta is compared per component as well as a vector."""
 import copy
 import functools
 import warnings
@@ -226,30 +229,44 @@ def test_real(case, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------- Roche fixed grid (all layouts)
+# Every Roche kernel runs one of three rhs bodies per launch (kv.roche_body): hill2_k1 (both Hill exponents exactly 2, one
+# dose per patient), hill2_kn (exponents 2, a loop over K dose times) and general (powf, and log_f32 in the Hill-exponent
+# gradients).  Each case's body is kv.body(case); theta, K and the inputs are part of the fp64 problem's key.
 def _theta_names(ablate):
     from oracle.rhs import THETA_NAMES
     return list(THETA_NAMES) + (["theta_1", "theta_2"] if ablate else [])
 
 
-def _roche_setup(D, ablate, N, T, seed):
+def _roche_setup(D, ablate, N, T, seed, theta=kv.THETA_DEFAULT, n_dose=1, neg_imm=False):
     from hode import synth
     from oracle.rhs import RocheRHS
-    inp = synth.solver_inputs(N, T, D, seed=seed)
+    inp = synth.solver_inputs(N, T, D, seed=seed, n_dose=n_dose)
+    if n_dose > 1:  # Dose(t) sums K decays of the patient's largest dose: keep it at one dose's scale, or the -Dose2 * ir
+        inp["actions"] /= n_dose  # term drives ir below zero inside a stage and ir ** HillPatho's log (grad theta) is NaN
+    if neg_imm:  # every other patient starts with a negative Immunity (the base of imm ** HillCure)
+        inp["z0"][::2, 2] = -0.05 - inp["z0"][::2, 2]
     torch.manual_seed(seed)
-    f = RocheRHS(D, synth.STEP, ablate=ablate)
+    f = RocheRHS(D, synth.STEP, ablate=ablate, theta=theta)
     if D > 4:
         with torch.no_grad():  # larger weights than default init so that the learned block matters
             f.ml_net[0].weight.mul_(2.0)
     return inp, f
 
 
+def _problem_key(case):
+    return (case.get("theta", "default"), case.get("hill"), case["n_dose"], bool(case.get("neg_imm")))
+
+
 @functools.lru_cache(maxsize=None)
-def _roche_problem(D, method, ablate):
-    """Inputs and the fp64 oracle of sum(h * cot) for one (D, method, rhs): shared by every layout and flag."""
+def _roche_problem(D, method, ablate, key=("default", None, 1, False)):
+    """Inputs and the fp64 oracle of sum(h * cot) for one (D, method, rhs, theta, K): shared by every layout and flag.
+    theta is the fp32 vector the kernels read, cast to double by the oracle's .double()."""
     from oracle.rhs import dose_schedule
     from oracle.solvers import odeint as oracle_odeint
+    th_name, hill, n_dose, neg_imm = key
+    theta = kv.theta_of(dict(theta=th_name, hill=hill))
     N, T = kv.ROCHE_N, kv.ROCHE_T
-    inp, f = _roche_setup(D, ablate, N, T, seed=100 + D + 7 * ablate)
+    inp, f = _roche_setup(D, ablate, N, T, seed=100 + D + 7 * ablate, theta=theta, n_dose=n_dose, neg_imm=neg_imm)
     cot = torch.randn(T, N, D, generator=torch.Generator().manual_seed(D))
     f.set_action(inp["actions"])
     f64 = copy.deepcopy(f).double()
@@ -263,6 +280,7 @@ def _roche_problem(D, method, ablate):
     if D > 4:
         ref["gw"], ref["gb"] = f64.ml_net[0].weight.grad, f64.ml_net[0].bias.grad
     dosage, times = dose_schedule(inp["actions"], f.step_size)
+    assert times.shape[1] == n_dose
     theta = torch.stack([getattr(f, n).detach().reshape(()) for n in _theta_names(ablate)])
     w = f.ml_net[0].weight.detach() if D > 4 else None
     b = f.ml_net[0].bias.detach() if D > 4 else None
@@ -290,18 +308,64 @@ def _roche_plan(p, dev, method, ablate, lanes, need_theta, tape):
     return out
 
 
+def _ref_finite(case, ref):
+    """The fp64 reference is finite everywhere, except in the negative-base case: there HillCure's gradient is
+    x ** p * log(x) with x < 0 (torch pow_backward_exponent), NaN, while the trajectory and every other gradient stay finite."""
+    for k, v in ref.items():
+        if case.get("neg_imm") and k == "gth":
+            assert torch.isnan(v[0]) and torch.isfinite(v[2:]).all(), v
+        else:
+            assert torch.isfinite(v).all(), (k, v)
+
+
+def _grad_ok(k, g, r, tol=1e-4):
+    """rel-L2 against the fp64 reference; a NaN the reference has (negative base, _ref_finite) the kernel must have at
+    exactly the same positions, and the rest is compared as usual."""
+    g, r = g.double().flatten().cpu(), r.double().flatten().cpu()
+    nan = torch.isnan(r)
+    assert torch.equal(torch.isnan(g), nan), (k, g, r)
+    err = _rel(g[~nan], r[~nan])
+    assert err <= tol, (k, err)
+    return err
+
+
+def _theta_components_ok(g, r, floor=None):
+    """grad_theta per component: |g_i - r_i| <= 1e-4 |r_i| + 1e-6 ||r||_2.  The Hill-exponent components are a small part
+    of ||r|| (grad kel dominates it), so the vector rel-L2 alone would let an error in them through.  The fp32 CPU oracle
+    on the fixed-grid problems of this file (every D, method, theta, K) sits at most 0.08 of this bound from fp64.
+    `floor` (per component) widens it where the fp32 evaluation of the same graph is itself further away (dopri5 with the
+    first step size attached, see test_dopri5_backward)."""
+    g, r = g.double().flatten().cpu(), r.double().flatten().cpu()
+    ok = torch.isfinite(r)
+    g, r = g[ok], r[ok]
+    bound = 1e-4 * r.abs() + 1e-6 * r.norm()
+    if floor is not None:
+        bound = torch.maximum(bound, floor[ok])
+    bad = ((g - r).abs() > bound).nonzero().flatten().tolist()
+    assert not bad, [(i, float(g[i]), float(r[i]), float(bound[i])) for i in bad]
+    return float(((g - r).abs() / bound).max()) if r.numel() else 0.0
+
+
+HILL_ULP_TOL = 1e-5  # rel-L2 between the general body at HillCure = 2 + 2^-22 and the x * x body at 2.0
+
+
 @pytest.mark.parametrize("case", _family("roche"), ids=kv.case_id)
-def test_roche_fixed_grid(case, monkeypatch):
+def test_roche_fixed_grid(case, monkeypatch, record_property):
     monkeypatch.delenv("HODE_RK_LAYOUT", raising=False)  # lanes = 0 must take the layout kv.roche_layout restates
     dev = _dev()
     D, method, ablate = case["D"], case["method"], case["ablate"]
-    p, ref = _roche_problem(D, method, ablate)
+    p, ref = _roche_problem(D, method, ablate, _problem_key(case))
+    _ref_finite(case, ref)
     got = _roche_plan(p, dev, method, ablate, case["lanes"], case["need_theta"], case["tape"])
     assert torch.equal(got["h"][0].cpu(), p["y0"])
     _traj_ok(got["h"], ref["h"])
+    record_property("body", kv.body(case))
+    record_property("err_h", (got["h"].double().cpu() - ref["h"]).abs().max().item() / (1 + ref["h"].abs().max().item()))
     for k in ("gy0", "gw", "gb", "gth"):
         if k in got:
-            assert _rel(got[k], ref[k]) <= 1e-4, (k, _rel(got[k], ref[k]))
+            record_property("err_" + k, _grad_ok(k, got[k], ref[k]))
+    if "gth" in got:
+        record_property("err_gth_comp", _theta_components_ok(got["gth"], ref["gth"]))
     if not case["need_theta"]:
         with_th = _roche_plan(p, dev, method, ablate, case["lanes"], True, case["tape"])
         assert torch.equal(got["h"], with_th["h"])
@@ -309,10 +373,18 @@ def test_roche_fixed_grid(case, monkeypatch):
         for k in ("gy0", "gw", "gb"):
             if k in got:
                 _same_as_with_theta(got[k], with_th[k], split or ablate, k)
+    if case["theta"] == "hill_ulp":
+        # the same call with HillCure exactly 2 runs the x * x body: continuous across the switch
+        p2 = dict(p, theta=p["theta"].clone())
+        p2["theta"][0] = 2.0
+        assert kv.roche_body(ablate, float(p2["theta"][0]), float(p2["theta"][1]), case["n_dose"]) == "hill2_k1"
+        at2 = _roche_plan(p2, dev, method, ablate, case["lanes"], case["need_theta"], case["tape"])
+        for k in got:
+            assert _rel(got[k], at2[k]) <= HILL_ULP_TOL, (k, _rel(got[k], at2[k]))
 
 
 # ------------------------------------------------------------------------------------------------------------ dopri5
-def _dp_gpu(inp, f, dev, lanes, need_theta):
+def _dp_gpu(inp, f, dev, lanes, need_theta, detach=True):
     from hode import adaptive
     from hode.solver import pack_theta
     from oracle.rhs import dose_schedule
@@ -324,36 +396,74 @@ def _dp_gpu(inp, f, dev, lanes, need_theta):
         b = f.ml_net[0].bias.detach().clone().to(dev).requires_grad_(True)
     dosage, times = dose_schedule(inp["actions"], f.step_size)
     h = adaptive.roche_dopri5(y0, pack_theta(scal, dev), w, b, inp["t"].to(dev), dosage.to(dev), times.to(dev), rtol=1e-7,
-                              atol=1e-8, ablate=f.ablate, lanes_per_patient=lanes, detach_first_step=True)
+                              atol=1e-8, ablate=f.ablate, lanes_per_patient=lanes, detach_first_step=detach)
     tape = adaptive.read_tape()
     (h * inp["cot"].to(dev)).sum().backward()
     torch.cuda.synchronize()
     out = dict(h=h.detach().cpu(), gy0=y0.grad.cpu())
     if w is not None:
         out["gw"], out["gb"] = w.grad.cpu(), b.grad.cpu()
+    if need_theta:
+        out["gth"] = torch.stack([s.grad for s in scal]).cpu()
     return out, tape
 
 
-@pytest.mark.parametrize("case", _family("dopri5"), ids=kv.case_id)
-def test_dopri5_backward(case):
-    """dp_bwd_kernel against the oracle's dopri5 step algebra replayed in fp64 along the kernel's own tape (first step size
-    detached on both sides, as test_hip_dopri5's case (a)), and need_theta=False against need_theta=True."""
+def _dp_case(case, dev, hill_cure=None):
+    """One dopri5 case: (the need_theta call, the other need_theta call, tape, inputs, rhs)."""
     from hode import adaptive
-    from test_hip_dopri5 import _replay
-    dev = _dev()
-    D, lanes, ablate = case["D"], case["lanes"], case["ablate"]
-    inp, f = _roche_setup(D, ablate, kv.DOPRI5_N, kv.DOPRI5_T, seed=40 + D + 5 * ablate)
+    D, ablate = case["D"], case["ablate"]
+    theta = kv.theta_of(case)
+    if hill_cure is not None:
+        theta = (hill_cure,) + theta[1:]
+    inp, f = _roche_setup(D, ablate, kv.DOPRI5_N, kv.DOPRI5_T, seed=40 + D + 5 * ablate, theta=theta, n_dose=case["n_dose"])
     inp["cot"] = torch.randn(kv.DOPRI5_T, kv.DOPRI5_N, D, generator=torch.Generator().manual_seed(3))
     adaptive.keep_workspace = True
     try:
-        got, tape = _dp_gpu(inp, f, dev, lanes, case["need_theta"])
-        other, _ = _dp_gpu(inp, f, dev, lanes, not case["need_theta"])
+        got, tape = _dp_gpu(inp, f, dev, case["lanes"], case["need_theta"], case["detach"])
+        other, _ = _dp_gpu(inp, f, dev, case["lanes"], not case["need_theta"], case["detach"])
     finally:
         adaptive.keep_workspace = False
+    return got, other, tape, inp, f
+
+
+@pytest.mark.parametrize("case", _family("dopri5"), ids=kv.case_id)
+def test_dopri5_backward(case, record_property):
+    """The dopri5 forward (dp_fwd_kernel, all three phases), the backward sweep (dp_bwd_kernel) and, with the first step
+    size attached, its backward (dp_initbwd_kernel passes 1 and 2) against the oracle's dopri5 step algebra replayed in
+    fp64 along the kernel's own tape (test_hip_dopri5's tape-replay oracle), grad_theta included; and need_theta=False
+    against need_theta=True.
+
+    First step detached: every gradient to rel-L2 1e-4.  Attached: d loss / d dt_0 is a cancellation-heavy fp32 sum (the
+    fp32 evaluation of the same graph on the same tape sits 1e-5 .. 7e-4 from fp64, test_hip_dopri5's case (b)), so there a
+    gradient is held to 1e-4 or to twice the fp32 replay's own distance from fp64 where that is larger, per vector and per
+    theta component."""
+    from test_hip_dopri5 import _replay
+    dev = _dev()
+    got, other, tape, inp, f = _dp_case(case, dev)
     assert len(tape["t"]) > 1 and tape["t"][0] == 0.0
-    ref = _replay(inp, f, 1e-7, 1e-8, inp["cot"], tape, False, double=True)
+    first = (not case["detach"]) and bool(tape["init"]["first_accepted"])
+    ref = _replay(inp, f, 1e-7, 1e-8, inp["cot"], tape, first, double=True)
+    for k, v in ref.items():
+        if k != "sigma":
+            assert torch.isfinite(v).all(), k
+    ref32 = _replay(inp, f, 1e-7, 1e-8, inp["cot"], tape, first) if first else None
     _traj_ok(got["h"], ref["h"])
-    for k in ("gy0", "gw", "gb"):
-        if k in got:
-            assert _rel(got[k], ref[k]) <= 1e-4, (k, _rel(got[k], ref[k]))
+    with_th = got if case["need_theta"] else other
+    record_property("body", kv.body(case))
+    record_property("err_h", (got["h"].double() - ref["h"]).abs().max().item() / (1 + ref["h"].abs().max().item()))
+    for k in ("gy0", "gw", "gb", "gth"):
+        if k not in with_th:
+            continue
+        g = got[k] if k in got else with_th[k]
+        rk = ref["gtheta" if k == "gth" else k]
+        tol = max(1e-4, 2.0 * _rel(ref32["gtheta" if k == "gth" else k], rk)) if first else 1e-4
+        record_property("err_" + k, _grad_ok(k, g, rk, tol))
+        if k != "gth":
             _same_as_with_theta(got[k], other[k], False, k)
+    floor = 2.0 * (ref32["gtheta"] - ref["gtheta"]).abs() if first else None
+    record_property("err_gth_comp", _theta_components_ok(with_th["gth"], ref["gtheta"], floor))
+    if case["theta"] == "hill_ulp":
+        at2, _, tape2, _, _ = _dp_case(case, dev, hill_cure=2.0)
+        assert len(tape2["t"]) == len(tape["t"])
+        for k in got:
+            assert _rel(got[k], at2[k]) <= HILL_ULP_TOL, (k, _rel(got[k], at2[k]))

@@ -1,18 +1,25 @@
 """Guard (no GPU): every compiled instantiation of the solver / decoder kernel families is launched by some entry of
 tests/kernel_variants.py's CASES -- the table tests/test_hip_kernel_variants.py runs against float64 -- or is listed as
 UNREACHABLE with a reason; and the restated dispatch rules agree with the library's own tile-dependent workspace sizes.
-A new tile class, method or flag that no test reaches fails here."""
+A new tile class, method or flag that no test reaches fails here.
+
+The Roche kernels branch at run time between inlined rhs bodies (kv.roche_body), which the symbols do not show: every
+(instantiation, body) pair must be reached by a case too, and the branch itself is read out of the kernel source and
+compared with kv.bodies(), so that a new body or a changed condition fails here as well."""
 import ctypes
 import glob
 import os
+import re
 import sys
 
+import numpy as np
 import pytest
 
 import kernel_variants as kv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "hybrid-ode-neurips-2021_amd", "csrc", "build")
+CSRC = os.path.join(ROOT, "hybrid-ode-neurips-2021_amd", "csrc")
+BUILD = os.path.join(CSRC, "build")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
@@ -63,6 +70,200 @@ def test_case_table_is_well_formed():
     assert len(ids) == len(set(ids))
     for c in kv.CASES:
         assert kv.kernels(c)
+
+
+def _pairs_covered():
+    cov = {}
+    for c in kv.CASES:
+        b = kv.body(c)
+        for n in kv.kernels(c):
+            if b in kv.bodies(n):
+                cov.setdefault((n, b), []).append(c)
+    return cov
+
+
+def test_every_roche_instantiation_body_pair_is_reached_by_a_case(compiled):
+    pairs = {(n, b) for n in compiled - set(kv.UNREACHABLE) for b in kv.bodies(n)}
+    assert len({n for n, _ in pairs}) >= 300  # every Roche family is in the build and counted
+    missing = sorted(pairs - set(_pairs_covered()) - set(kv.UNREACHABLE_BODIES))
+    assert not missing, "%d (instantiation, body) pairs no CASES entry reaches:\n  %s" % (
+        len(missing), "\n  ".join("%s  %s" % p for p in missing))
+    assert set(kv.UNREACHABLE_BODIES) <= pairs and not set(kv.UNREACHABLE_BODIES) & set(_pairs_covered())
+
+
+def test_every_roche_case_names_its_body():
+    for c in kv.CASES:
+        ks = kv.kernels(c)
+        if c["family"] in ("roche", "dopri5"):
+            b = kv.body(c)
+            assert c["theta"] in ("default", "general", "hill_ulp") and c["n_dose"] in (0, 1, 2, 3), c
+            assert all(b in kv.bodies(n) for n in ks if kv.family(n) in kv.ROCHE_FAMILIES), c
+            assert any(kv.family(n) in kv.ROCHE_FAMILIES for n in ks), c
+        else:
+            assert kv.body(c) is None and not any(kv.bodies(n) for n in ks)
+
+
+def test_roche_body_rule():
+    th = kv.theta_of
+    assert kv.roche_body(False, 2.0, 2.0, 1) == "hill2_k1"
+    for K in (0, 2, 3):
+        assert kv.roche_body(False, 2.0, 2.0, K) == "hill2_kn"
+        assert kv.roche_body(True, 2.5, 1.5, K) == "hill2_kn"  # ABLATE forces hill2
+    assert kv.roche_body(True, 3.0, 1.0, 1) == "hill2_k1"
+    assert kv.HILL_ULP == float(np.nextafter(np.float32(2.0), np.float32(3.0)))
+    assert kv.roche_body(False, *th(dict(theta="hill_ulp"))[:2], 1) == "general"
+    for hill in kv.GENERAL_HILL + (kv.NEG_BASE_HILL,):
+        t = th(dict(theta="general", hill=hill))
+        assert len(t) == 13 and kv.roche_body(False, t[0], t[1], 1) == "general"
+    assert any(2.0 not in th(dict(theta="general", hill=h))[:2] for h in kv.GENERAL_HILL)
+    assert any(th(dict(theta="general", hill=h))[:2].count(2.0) == 1 for h in kv.GENERAL_HILL)
+    assert kv.bodies("hode::split_bwd_kernel<12, 2, false, true, true>") == ("hill2_k1", "hill2_kn", "general")
+    assert kv.bodies("hode::rk_fwd_kernel<8, 4, 2, true>") == ("hill2_k1", "hill2_kn")
+    assert kv.bodies("hode::dp_initbwd_kernel<8, 4, true, false, 1>") == ("hill2_k1", "hill2_kn")
+    assert kv.bodies("hode::dp_persist_kernel<8, false>") == ("hill2_k1", "hill2_kn", "general")
+    assert kv.bodies("hode::split_fold_kernel") == ()
+
+
+def test_general_hill_cases_cover_the_split_layout():
+    for D in (8, 12):
+        for method in kv.METHODS:
+            assert any(c["family"] == "roche" and kv.body(c) == "general" and c["D"] == D and c["method"] == method
+                       and kv.roche_layout(D, c["lanes"], kv.ROCHE_T) == "split" for c in kv.CASES), (D, method)
+
+
+# ----------------------------------------------------------------------------- the runtime branch in the kernel source
+ROCHE_SOURCES = ("hode_rk_kernels.hpp", "hode_rk_split.hip", "hode_rk_mf.hip", "hode_dopri5_kernels.hpp")
+# the hill2 definitions kv.roche_body restates (whitespace normalised); dp_* attempt launches: decided by the host
+HILL2_DEFS = ("ABLATE || (a.theta[0] == 2.0f && a.theta[1] == 2.0f)",
+              "ABLATE || (a.hill2 >= 0 ? a.hill2 != 0 : (a.theta[0] == 2.0f && a.theta[1] == 2.0f))",
+              "ABLATE || a.hill2 != 0")
+# condition of the runtime if / else-if / else chain -> (HILL2, K1) of the call it guards
+BRANCH_CONDS = {"hill2 && a.K == 1": (True, True), "hill2": (True, False), None: (False, False)}
+
+
+def _norm(x):
+    return " ".join(x.split())
+
+
+def _strip_and_expand(src):
+    """Comments removed, line continuations joined, and the function-like macros defined in the file expanded (e.g.
+    HODE_DP_DISPATCH(BODY) in hode_dopri5_kernels.hpp)."""
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    src = src.replace("\\\n", " ")
+    for name, arg, body in re.findall(r"^[ \t]*#define[ \t]+(\w+)\((\w+)\)([^\n]*)$", src, flags=re.M):
+        src = re.sub(r"^[ \t]*#define[ \t]+%s\(.*$" % name, "", src, flags=re.M)
+        src = re.sub(r"\b%s\((\w+)\)" % name, lambda m: re.sub(r"\b%s\b" % arg, m.group(1), body), src)
+    return src
+
+
+def _match(src, i, open_, close):
+    """Index one past the bracket that closes src[i] (== open_)."""
+    depth = 0
+    for j in range(i, len(src)):
+        if src[j] == open_:
+            depth += 1
+        elif src[j] == close:
+            depth -= 1
+            if depth == 0:
+                return j + 1
+    raise ValueError("unbalanced %s" % open_)
+
+
+def _constexpr_arms(body):
+    """The arms of a top-level `if constexpr (...) {...} else if constexpr (...) {...} else {...}` chain, each with the
+    text outside the chain appended; [body] when there is none."""
+    m = re.search(r"\bif constexpr\s*\(", body)
+    if not m:
+        return [body]
+    arms, i, start = [], m.start(), m.start()
+    while True:
+        j = _match(body, body.index("(", i), "(", ")")
+        k = body.index("{", j)
+        assert not body[j:k].strip(), body[i:k]
+        e = _match(body, k, "{", "}")
+        arms.append(body[k + 1:e - 1])
+        rest = body[e:]
+        m2 = re.match(r"\s*else\s+if constexpr\s*\(", rest)
+        if m2:
+            i = e + m2.end() - 1
+            i = body.rindex("if", e, i)
+            continue
+        m3 = re.match(r"\s*else\s*\{", rest)
+        if m3:
+            k = e + m3.end() - 1
+            e2 = _match(body, k, "{", "}")
+            arms.append(body[k + 1:e2 - 1])
+            e = e2
+        outside = body[:start] + body[e:]
+        return [a + outside for a in arms]
+
+
+def roche_source_branches(csrc=CSRC):
+    """{kernel: [set of (HILL2, K1) per if-constexpr arm]} for every __global__ Roche kernel in ROCHE_SOURCES, with every
+    runtime branch's condition checked against BRANCH_CONDS and the hill2 definition against HILL2_DEFS."""
+    out = {}
+    for fn in ROCHE_SOURCES:
+        src = _strip_and_expand(open(os.path.join(csrc, fn)).read())
+        params = {}  # body function -> (index of HILL2, index of K1) in its template parameter list
+        for tp, name in re.findall(r"template\s*<([^<>]*)>\s*HODE_DEV\s+void\s+(\w+)\s*\(", src):
+            names = [p.split()[-1] for p in tp.split(",")]
+            if "HILL2" in names and "K1" in names:
+                params[name] = (names.index("HILL2"), names.index("K1"))
+        for m in re.finditer(r"template\s*<[^<>]*>\s*__global__[^{;]*?\bvoid\s+(\w+)\s*\([^()]*\)\s*\{", src):
+            kname, k = m.group(1), m.end() - 1
+            body = src[k + 1:_match(src, k, "{", "}") - 1]
+            calls = re.findall(r"\b(\w+)\s*<[^<>]*>\s*\(", body)
+            if not any(c in params for c in calls):
+                continue
+            defs = re.findall(r"const bool hill2 = ([^;]*);", body)
+            assert len(defs) == 1 and _norm(defs[0]) in HILL2_DEFS, (fn, kname, defs)
+            arms = []
+            for arm in _constexpr_arms(body):
+                pairs = []
+                for kw, cond, callee, targs in re.findall(
+                        r"(else\s+if|if|else)\s*(?:\(([^()]*)\))?\s*(\w+)\s*<([^<>]*)>\s*\(", arm):
+                    if callee not in params:
+                        continue
+                    args = [x.strip() for x in targs.split(",")]
+                    ih, ik = params[callee]
+                    assert args[ih] in ("true", "false") and args[ik] in ("true", "false"), (kname, callee, targs)
+                    pair = (args[ih] == "true", args[ik] == "true")
+                    key = _norm(cond) if kw.strip() != "else" else None
+                    assert key in BRANCH_CONDS and BRANCH_CONDS[key] == pair, (fn, kname, kw, cond, callee, pair)
+                    pairs.append(pair)
+                assert pairs and len(pairs) == len(set(pairs)), (fn, kname, pairs)
+                arms.append(set(pairs))
+            assert kname not in out, kname
+            out[kname] = arms
+    return out
+
+
+def test_roche_source_branches_match_the_body_rule(compiled):
+    """Every (HILL2, K1) pair a Roche kernel's source dispatches, per if-constexpr arm, is a body kv.bodies() lists for its
+    instantiations: all three for the full rhs; with ABLATE = true the hill2 definition (ABLATE || ...) leaves the
+    HILL2 = true calls.  dp_bwd_kernel has six calls, three per arm."""
+    src = roche_source_branches()
+    assert set(src) == set(kv.ROCHE_FAMILIES), sorted(set(src) ^ set(kv.ROCHE_FAMILIES))
+    assert len(src["dp_bwd_kernel"]) == 2 and len(src["dp_fwd_kernel"]) == 4
+    seen = set()
+    for n in compiled:
+        fam = kv.family(n)
+        if fam not in kv.ROCHE_FAMILIES:
+            continue
+        seen.add(fam)
+        want = {kv.BODY_ARGS[b] for b in kv.bodies(n)}
+        for arm in src[fam]:
+            live = {p for p in arm if p[0] or not kv._ablate_arg(n)}
+            assert live == want, (n, sorted(live), sorted(want))
+    assert seen == set(kv.ROCHE_FAMILIES)
+
+
+def test_host_hill2_read_back_is_the_same_comparison():
+    """The dopri5 attempt launches take hill2 from the host (csrc/hode_dopri5.hip): the comparison kv.roche_body restates."""
+    src = _norm(_strip_and_expand(open(os.path.join(CSRC, "hode_dopri5.hip")).read()))
+    assert "a.hill2 = (hill[0] == 2.0f && hill[1] == 2.0f) ? 1 : 0;" in src
+    assert "a.hill2 = -1;" in src
 
 
 def test_kernel_name_normalisation():
