@@ -6,7 +6,13 @@ Workload (BASELINE.json configs[1]): dim=12 synthetic, 10 000 patients PER GPU, 
 rank's batch (+ one RCCL all-reduce of the parameter-gradient bucket when N>1).  Inputs are resident in HBM
 before the timed region.  Rank 0 prints ONE JSON line.
 
-Besides the headline the default run also measures (same shape, same patients):
+A plain run does only what the headline needs: it sets up, pre-conditions and warms up, times the K steps, writes
+`--dump-outputs`, and prints the line (metric, value, unit, ms_per_step, dtype, config).  `--dump-outputs DIR` writes what
+the last timed step computed (rank 0: trajectory h and the adjoint's gradients) as float32 DIR/<name>.npy, for
+output-for-output comparison of two builds on the same seeded inputs.
+
+`--full` measures and checks, after the timed steps, everything else (same shape, same patients):
+  * "roofline"           -- the forward and adjoint kernels alone, timed by HIP events in runs of their own, against HBM
   * "parity"             -- the shipped kernels (split layout + stage tape + hipGraph) against the CPU oracle on ALL
                             10 000 patients of this very run: trajectory MSE / max-abs, gradient rel-L2
   * "cpu_baseline"       -- that oracle, timed: 3 warm-up + 5 repetitions, median, all host cores of the share
@@ -14,11 +20,10 @@ Besides the headline the default run also measures (same shape, same patients; S
                             (MFMA fraction), cpu_baseline and parity (oracle pipeline on a sample)
   * "dopri5_step"        -- BASELINE config 3 per GPU: adaptive solve + tape adjoint, with roofline (per attempt),
                             cpu_baseline and parity (the oracle's step algebra replayed along the run's own tape)
-`--headline-only` skips the two extra blocks, `--no-cpu` every CPU leg.  `--dump-outputs DIR` writes what the last timed
-step computed (rank 0: trajectory h and the adjoint's gradients) as float32 DIR/<name>.npy, for output-for-output
-comparison of two builds on the same seeded inputs.
+  * "other_configs"      -- BASELINE config 5 and the NeuralODE rhs, timed (single GPU)
+With `--full`, `--headline-only` skips the last three blocks and `--no-cpu` every CPU leg.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 `python bench.py --gpus N` without a launcher starts that command itself (before anything touches the GPU).
@@ -28,7 +33,7 @@ child.  The default gradient exchange is the all-reduce captured inside the step
 between torch's and RCCL's streams); each rank guards the first replays with its own watchdog (exit code 17 if they do
 not finish), and the supervisors then start FRESH ranks on the overlap path (async all-reduce on alternating buckets)
 under a new store prefix; `config.grad_exchange` / `config.grad_exchange_fallback` say which path the numbers come from.
-At N > 1 every rank also runs `full_training_step` (with the flat-bucket all-reduce of `training_utils`) and
+With `--full` at N > 1 every rank also runs `full_training_step` (with the flat-bucket all-reduce of `training_utils`) and
 `dopri5_step`, so a scaling run yields the solver-only, the full-step and the dopri5 curve.  CPU rehearsal of this
 control flow: tests/test_bench_dist.py (gloo, world size 2, HODE_BENCH_STUB).
 
@@ -621,6 +626,33 @@ def kernel_times(plan, iters=20):
     return fwd, bwd_kernel, bwd_call
 
 
+def headline_roofline(plan, kt, step_s, tape=True, stub=False):
+    """--full: the headline's `roofline` block -- the adjoint and forward kernels alone (`kernel_times`, None for the stub)
+    against HBM, the whole step's share of HBM, and the traffic counters of the newest committed profile."""
+    fwd_s, bwd_s, bwd_call_s = kt if kt is not None else (1.0, 1.0, 1.0)
+    ach = plan.bwd_bytes / bwd_s / 1e9
+    roof = {"bound": "hbm", "kernel": "split_bwd_kernel<12, rk4> (adjoint kernel alone; the whole backward call incl. "
+                                      "the partial fold is bwd_call_us)", "achieved": ach,
+            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
+            "bytes_per_launch": plan.bwd_bytes, "avg_launch_us": bwd_s * 1e6, "bwd_call_us": bwd_call_s * 1e6,
+            "fwd": {"bytes_per_launch": plan.fwd_bytes, "avg_launch_us": fwd_s * 1e6,
+                    "achieved": plan.fwd_bytes / fwd_s / 1e9, "frac": plan.fwd_bytes / fwd_s / 1e9 / HBM_PEAK_GBS},
+            "step_frac": (plan.fwd_bytes + plan.bwd_bytes) / step_s / 1e9 / HBM_PEAK_GBS}
+    tr = pmc_traffic(tape=tape) if not stub else None
+    if tr is not None:
+        roof["traffic"] = tr["bytes_per_launch"]
+        roof["traffic_source"] = "committed profile " + tr["source"] + " (rocprofv3 --pmc, not collected in this run)"
+        if tr.get("valu_active_frac") is not None:
+            # the second roofline of this kernel: it is issue bound (DESIGN.md 4.3c): share of the wave's cycles
+            # in which it issues a VALU instruction, from the same committed --pmc pass
+            roof["issue"] = {"valu_active_frac": tr["valu_active_frac"], "source": tr["source"]}
+    if tape:
+        # deliberate recompute <-> traffic trade (DESIGN.md 4.3c): the forward leaves the 3 intermediate expert stage
+        # states of every step (16 B each) and the backward reads them back instead of re-integrating
+        roof["tape_bytes_per_launch"] = (T - 1) * 3 * N_PER_GPU * 16 + (T - 1) * N_PER_GPU * (D - 4) * 2 * 4  # expert stage states + 2 learned stage derivatives
+    return roof
+
+
 GUARD_EXIT = 17   # exit code of a rank whose guarded phase (graph-captured collective) did not finish in time
 
 
@@ -750,8 +782,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu", action="store_true", help="skip every CPU leg (baselines and parity)")
-    ap.add_argument("--headline-only", action="store_true", help="skip the full_training_step and dopri5_step blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check what the headline does not need: kernel roofline, CPU "
+                         "baseline and parity, full_training_step, dopri5_step, other_configs")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip every CPU leg (baselines and parity)")
+    ap.add_argument("--headline-only", action="store_true",
+                    help="with --full: skip the full_training_step, dopri5_step and other_configs blocks")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a HIP graph")
     ap.add_argument("--lanes", type=int, default=0, help="force lanes per patient (1|4), 0 = library default")
     ap.add_argument("--no-theta-grad", action="store_true", help="skip the 13 expert-constant gradients")
@@ -948,11 +984,11 @@ def main():
         dump_outputs(args.dump_outputs, plan, plan.buckets[last_bucket[0]] if overlap else plan.grad_flat, stub,
                      not args.no_theta_grad)
 
-    extras = not args.headline_only and not stub
-    cpu = not args.no_cpu and world == 1 and not stub
-    # ---- every GPU measurement first (the card clocks down while the host runs the CPU legs), then the CPU legs
+    # ---- --full: every GPU measurement first (the card clocks down while the host runs the CPU legs), then the CPU legs
+    extras = args.full and not args.headline_only and not stub
+    cpu = args.full and not args.no_cpu and world == 1 and not stub
     gpu = kt = None
-    if rank == 0 and not stub:
+    if args.full and rank == 0 and not stub:
         kt = kernel_times(plan)
         # what the timed kernels left in HBM for one step (single rank: the bucket IS this rank's gradient)
         if use_graph:
@@ -968,10 +1004,8 @@ def main():
     dp, dp_cpu = dopri5_step(dev, rank, prob, dist, cpu=cpu) if extras else (None, None)
     if rank == 0:
         others = other_configs(dev) if extras and world == 1 else None
-        fwd_s, bwd_s, bwd_call_s = kt if kt is not None else (1.0, 1.0, 1.0)
         ms = elapsed / args.steps * 1e3
         total = N_PER_GPU * world
-        ach = plan.bwd_bytes / bwd_s / 1e9
         exchange_text = {None: None, "graph": "rccl all-reduce(AVG), captured in the step graph",
                          "overlap": "rccl all-reduce(AVG), async under the next solve", "sync": "rccl all-reduce(AVG), serialised"}[mode]
         out = {
@@ -997,27 +1031,11 @@ def main():
                        "preconditioning": {"replays": n_pre, "ms": pre_ms,
                                            "why": "untimed replays of the same step ahead of the W warm-up steps: from idle the card's "
                                                   "clock ramps for ~25 ms (profiles/r03_v0_clock_ramp.txt)"}},
-            "roofline": {"bound": "hbm", "kernel": "split_bwd_kernel<12, rk4> (adjoint kernel alone; the whole backward call incl. "
-                                                      "the partial fold is bwd_call_us)", "achieved": ach,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
-                         "bytes_per_launch": plan.bwd_bytes, "avg_launch_us": bwd_s * 1e6, "bwd_call_us": bwd_call_s * 1e6,
-                         "fwd": {"bytes_per_launch": plan.fwd_bytes, "avg_launch_us": fwd_s * 1e6,
-                                 "achieved": plan.fwd_bytes / fwd_s / 1e9, "frac": plan.fwd_bytes / fwd_s / 1e9 / HBM_PEAK_GBS},
-                         "step_frac": (plan.fwd_bytes + plan.bwd_bytes) / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS},
         }
-        tr = pmc_traffic(tape=not args.no_tape) if not stub else None
-        if tr is not None:
-            out["roofline"]["traffic"] = tr["bytes_per_launch"]
-            out["roofline"]["traffic_source"] = "committed profile " + tr["source"] + " (rocprofv3 --pmc, not collected in this run)"
-            if tr.get("valu_active_frac") is not None:
-                # the second roofline of this kernel: it is issue bound: share of the wave's cycles
-                # in which it issues a VALU instruction, from the same committed --pmc pass
-                out["roofline"]["issue"] = {"valu_active_frac": tr["valu_active_frac"], "source": tr["source"]}
         if not args.no_tape:
-            # deliberate recompute <-> traffic trade: the forward leaves the 3 intermediate expert stage
-            # states of every step (16 B each) and the backward reads them back instead of re-integrating
-            out["roofline"]["tape_bytes_per_launch"] = (T - 1) * 3 * N_PER_GPU * 16 + (T - 1) * N_PER_GPU * (D - 4) * 2 * 4  # expert stage states + 2 learned stage derivatives
             out["config"]["stage_tape"] = True
+        if args.full:
+            out["roofline"] = headline_roofline(plan, kt, elapsed / args.steps, tape=not args.no_tape, stub=stub)
         if cpu:
             out["cpu_baseline"], out["parity"] = cpu_baseline_and_parity(prob, gpu)
             out["speedup_vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]

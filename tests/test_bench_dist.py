@@ -91,3 +91,19 @@ def test_dump_outputs_writes_the_last_steps_all_reduced_bucket(tmp_path, exchang
     g = np.load(out_dir / "grad_flat.npy")
     assert g.dtype == np.float32 and g.shape == (120,)
     assert (g == 3.0).all()
+
+
+HEADLINE_KEYS = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                 "vs_baseline", "dtype", "data", "config"]
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_a_plain_run_carries_the_headline_only_and_full_adds_the_rest(full):
+    """A plain run prints the headline fields and its config, nothing that takes runs of its own; --full adds the
+    headline's roofline (the extra blocks and CPU legs stay off under the stub)."""
+    r, lines = _run(_launcher(_free_port()) + (["--full"] if full else []), {})
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert list(out) == HEADLINE_KEYS + (["roofline"] if full else [])
+    assert out["steps"] == 5 and out["warmup"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0

@@ -7,15 +7,15 @@ export TMPDIR=/tmp
 O=gpurun_out/r03_final
 mkdir -p $O
 timeout -k 10 1000 python3 -m pytest tests -q -m gpu > $O/tests.log 2>&1; echo "tests rc=$?"; tail -6 $O/tests.log | cut -c 1-300
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-rocprofv3 --kernel-trace --stats -d $O/stats -o s --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err; echo "stats rc=$?"
+timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+rocprofv3 --kernel-trace --stats -d $O/stats -o s --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err; echo "stats rc=$?"
 pass() {
   tag=$1; name=$2; prog=$3; shift 3
   rocprofv3 --pmc "$@" -d $O/$tag/pmc_$name -o c --output-format csv -- python3 $prog > $O/${tag}_pmc_$name.log 2>&1 || { echo "pmc $tag $name failed"; tail -3 $O/${tag}_pmc_$name.log; return 1; }
   echo "pmc $tag $name done"
 }
 for tag in lstm split; do
-  if [ $tag = lstm ]; then prog="tools/lstm_train_probe.py"; else prog="bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --headline-only"; fi
+  if [ $tag = lstm ]; then prog="tools/lstm_train_probe.py"; else prog="bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --headline-only"; fi
   pass $tag fetch "$prog" FETCH_SIZE &&
   pass $tag write "$prog" WRITE_SIZE &&
   pass $tag sq1 "$prog" SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU &&
