@@ -104,15 +104,15 @@ int lstm_geom(const hode_lstm_desc* d, LstmGeom* G, bool bwd_compatible) {
   G->LD = G->BT + ((G->BT % 32 == 0) ? 16 : 0);
   G->wp_floats = (size_t)4 * G->KQ4 * G->TPW * 64 * 4;
   G->tape_floats = (size_t)d->seq_len * G->nblk * 4 * G->TPW * G->NT * 5 * 64;
-  G->lds_bytes = (size_t)2 * 4 * G->Kq * G->LD * sizeof(float);
-  if (G->lds_bytes > 160 * 1024)
-    return hode::fail(HODE_E_UNSUPPORTED, "lstm: activation tile needs %zu B of LDS (> 160 KiB)", G->lds_bytes);
+  // the staging registers bound the tile first; the LDS bound is checked on the tile that is launched
   while (G->NT > 1 && (size_t)16 * G->NT * d->obs_dim > 5120) --G->NT;
   G->BT = 16 * G->NT;
   G->nblk = (d->batch + G->BT - 1) / G->BT;
   G->LD = G->BT + ((G->BT % 32 == 0) ? 16 : 0);
   G->tape_floats = (size_t)d->seq_len * G->nblk * 4 * G->TPW * G->NT * 5 * 64;
   G->lds_bytes = (size_t)2 * 4 * G->Kq * G->LD * sizeof(float);
+  if (G->lds_bytes > 160 * 1024)
+    return hode::fail(HODE_E_UNSUPPORTED, "lstm: activation tile needs %zu B of LDS (> 160 KiB)", G->lds_bytes);
   G->whp_floats = (size_t)4 * G->TPW * 4 * ((G->TPW + 3) / 4) * 64 * 4;
   {
     const size_t tile = (size_t)G->BT * (4 * Hp + 4), slabs = (size_t)4 * Hp * G->LD;

@@ -54,7 +54,6 @@ class _NeuralFixedGrid(torch.autograd.Function):
         method, perturb = ctx.meta
         lib = L.lib()
         T, B, D = h.shape
-        HD = w1c.shape[0]
         gh = grad_h.to(torch.float32).contiguous()
         gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)
         d = _desc(h[0], tc, dosc, dtc, w1c, b1c, w2c, b2c, h, method, perturb)
@@ -70,30 +69,39 @@ class _NeuralFixedGrid(torch.autograd.Function):
             L.check(lib.hode_rk_bwd(d, _stream()), "hode_rk_bwd[neural]")
         if onchip:
             return gy0, gw1, gb1, gw2, gb2, None, None, None, None, None
-        off = (C.c_size_t * 4)()
-        L.check(lib.hode_neural_tape_offsets(d, off), "hode_neural_tape_offsets")
-        inst = (T - 1) * _STAGES[method]
+        return (gy0,) + contract_tape(ws, d, T, B, D, method) + (None, None, None, None, None)
 
-        def tape(k, rows):
-            return ws[off[k]: off[k] + inst * rows * B * 4].view(torch.float32).view(inst, rows, B)
 
-        if inst == 0:
-            z = torch.zeros_like
-            return gy0, z(w1c), z(b1c), z(w2c), z(b2c), None, None, None, None, None
-        a1t, u1t, yet, u2t = tape(0, HD), tape(1, HD), tape(2, D + 1), tape(3, D)
-        # sums over the instance axis as (1 x inst) GEMMs, over patients as GEMVs with a ones vector: torch's strided
-        # reductions over these shapes run at a fraction of the HBM rate
-        ones_i = torch.ones((1, inst), device=h.device, dtype=torch.float32)
-        ones_b = torch.ones((B, 1), device=h.device, dtype=torch.float32)
+def contract_tape(ws, d, T, B, D, method):
+    """(gw1, gb1, gw2, gb2) from the operand tapes a tape-writing backward left in its workspace ``ws`` (descriptor ``d``,
+    offsets from ``hode_neural_tape_offsets``): per stage instance a1 / u1 (10 D rows), [y, Dose] (D + 1 rows) and u2 (D rows)
+    of ``B`` floats each (the lane-per-patient kernels, and the matrix-core backward when the caller passes no grad_w1)."""
+    lib = L.lib()
+    HD = 10 * D
+    off = (C.c_size_t * 4)()
+    L.check(lib.hode_neural_tape_offsets(d, off), "hode_neural_tape_offsets")
+    inst = (T - 1) * _STAGES[method]
 
-        def fold(part):  # (inst, m, n) -> (m, n)
-            return (ones_i @ part.reshape(inst, -1)).view(part.shape[1], part.shape[2])
+    def tape(k, rows):
+        return ws[off[k]: off[k] + inst * rows * B * 4].view(torch.float32).view(inst, rows, B)
 
-        gw1 = fold(torch.bmm(u1t, yet.transpose(1, 2)))
-        gw2 = fold(torch.bmm(u2t, a1t.transpose(1, 2)))
-        gb1 = fold(u1t @ ones_b).reshape(-1)
-        gb2 = fold(u2t @ ones_b).reshape(-1)
-        return gy0, gw1, gb1, gw2, gb2, None, None, None, None, None
+    if inst == 0:
+        z = lambda *s: torch.zeros(s, device=ws.device, dtype=torch.float32)  # noqa: E731
+        return z(HD, D + 1), z(HD), z(D, HD), z(D)
+    a1t, u1t, yet, u2t = tape(0, HD), tape(1, HD), tape(2, D + 1), tape(3, D)
+    # sums over the instance axis as (1 x inst) GEMMs, over patients as GEMVs with a ones vector: torch's strided
+    # reductions over these shapes run at a fraction of the HBM rate
+    ones_i = torch.ones((1, inst), device=ws.device, dtype=torch.float32)
+    ones_b = torch.ones((B, 1), device=ws.device, dtype=torch.float32)
+
+    def fold(part):  # (inst, m, n) -> (m, n)
+        return (ones_i @ part.reshape(inst, -1)).view(part.shape[1], part.shape[2])
+
+    gw1 = fold(torch.bmm(u1t, yet.transpose(1, 2)))
+    gw2 = fold(torch.bmm(u2t, a1t.transpose(1, 2)))
+    gb1 = fold(u1t @ ones_b).reshape(-1)
+    gb2 = fold(u2t @ ones_b).reshape(-1)
+    return gw1, gb1, gw2, gb2
 
 
 def neural_solve(y0, w1, b1, w2, b2, t, dosage, dose_times, method="rk4", perturb=False):

@@ -30,7 +30,14 @@ FAMILIES = ("tlstm_fwd_kernel", "tlstm_bwd_kernel", "gruode_fwd_kernel", "gruode
             "real_mf_kernel", "real_grad_fold_kernel", "real_kernel",
             "rk_fwd_kernel", "rk_bwd_kernel", "split_fwd_kernel", "split_bwd_kernel", "split_fold_kernel",
             "mf_fwd_kernel", "mf_bwd_kernel", "mf_fold_kernel", "dp_fwd_kernel", "dp_bwd_kernel", "dp_initbwd_kernel",
-            "dp_persist_kernel")
+            "dp_persist_kernel",
+            # NeuralODE rhs: fixed grid (matrix-core and lane layouts), dopri5
+            "neural_mf_fwd_kernel", "neural_mf_bwd_kernel", "neural_grad_fold_kernel", "neural_fwd_kernel",
+            "neural_bwd_kernel", "transpose_w2_kernel", "ndp_fwd_kernel", "ndp_bwd_kernel", "ndp_initbwd_kernel",
+            # LSTM encoder
+            "lstm_fwd_kernel", "lstm_bwd_kernel", "lstm_fill_operand_kernel", "lstm_pack_kernel", "lstm_pack_hh_kernel",
+            # readouts
+            "readout_sse_kernel", "readout_mf_kernel", "readout_fold_kernel", "readout_mlp_kernel", "readout_mlp_fold_kernel")
 # the families whose kernels branch between the Roche rhs bodies (roche_body)
 ROCHE_FAMILIES = ("rk_fwd_kernel", "rk_bwd_kernel", "split_fwd_kernel", "split_bwd_kernel", "mf_fwd_kernel", "mf_bwd_kernel",
                   "dp_fwd_kernel", "dp_bwd_kernel", "dp_initbwd_kernel", "dp_persist_kernel")
@@ -170,6 +177,144 @@ def dopri5_kernels(D, lanes, ablate, need_theta, detach_first_step=True, B=21):
         out += ["hode::dp_initbwd_kernel<%d, %d, %s, false, 1>" % (D, lpp, a),
                 "hode::dp_initbwd_kernel<%d, %d, %s, %s, 2>" % (D, lpp, a, _b(need_theta))]
     return out
+
+
+def neural_layout(D, env=None):
+    """csrc/hode_neural.hip:355-361 neural_rk: the one-patient-per-lane kernels when HODE_NEURAL_LAYOUT starts with 't'
+    (compiled for D = 6, 8, 12 only, anything else is a configuration error); the matrix-core kernels otherwise."""
+    if env and env[0] == "t":
+        assert D in (6, 8, 12), D
+        return "lane"
+    return "mf"
+
+
+def neural_fixed(D, method, env=None, onchip=True):
+    """Fixed-grid NeuralODE forward + backward (onchip = the caller hands grad_w1, hode.neural's default).
+    mf: csrc/hode_neural_mf.hip:188-203 launch_neural_mf_d: grid ceil(B/16); neural_mf_bwd_kernel<D, M, ONCHIP> with
+    ONCHIP = bwd && grad_w1 (:190), and the on-chip backward folds its per-wave partials with neural_grad_fold_kernel<D>
+    (:200).  lane: csrc/hode_neural.hip:318-328 launch_neural: grid ceil(B/64), after transpose_w2_kernel (:362, every
+    call); its backward always writes the operand tapes (csrc/hode_neural.hip:273 neural_onchip)."""
+    if neural_layout(D, env) == "lane":
+        return ["hode::transpose_w2_kernel", "hode::neural_fwd_kernel<%d, %d>" % (D, method),
+                "hode::neural_bwd_kernel<%d, %d>" % (D, method)]
+    out = ["hode::neural_mf_fwd_kernel<%d, %d>" % (D, method),
+           "hode::neural_mf_bwd_kernel<%d, %d, %s>" % (D, method, _b(onchip))]
+    return out + (["hode::neural_grad_fold_kernel<%d>" % D] if onchip else [])
+
+
+def neural_grid(B, layout):
+    """Workgroups of one launch: csrc/hode_neural_mf.hip:189 (16 patients per wave), csrc/hode_neural.hip:319 (64)."""
+    return (B + 15) // 16 if layout == "mf" else (B + 63) // 64
+
+
+NEURAL_DOPRI5_DIMS = (4, 6, 8, 10, 12, 14)  # csrc/hode_neural_dopri5.hip:610 HODE_ND_DIMS
+
+
+def neural_dopri5_kernels(D, n_acc, detach_first_step):
+    """csrc/hode_neural_dopri5.hip:554-563 nd_fwd: phases 0 / 1 (initial step) and 2 (attempts) of ndp_fwd_kernel<D, PHASE>;
+    :596-602 nd_bwd: ndp_bwd_kernel<D> and the fold of its partials, then, when a step was accepted (n_acc > 0) and the
+    first step size is not detached (HODE_FLAG_DETACH_FIRST_STEP), ndp_initbwd_kernel<D, 1>, <D, 2> and the fold again."""
+    out = ["hode::ndp_fwd_kernel<%d, %d>" % (D, ph) for ph in (0, 1, 2)]
+    out += ["hode::ndp_bwd_kernel<%d>" % D, "hode::neural_grad_fold_kernel<%d>" % D]
+    if n_acc > 0 and not detach_first_step:
+        out += ["hode::ndp_initbwd_kernel<%d, 1>" % D, "hode::ndp_initbwd_kernel<%d, 2>" % D]
+    return out
+
+
+LSTM_SIZES = (16, 32, 48, 64, 80, 96, 128, 160)  # csrc/hode_lstm.hip:85 kSizes
+LSTM_TPWS = tuple(h // 16 for h in LSTM_SIZES)   # build_hip.py LSTM_TPWS: one hode_lstm_tpw.hip unit per padded size
+
+
+def choose_nt(B, save_tape):
+    """csrc/hode_lstm.hip:71-80 choose_nt: NT <= 3 with a tape (the backward's limit), <= 4 without; the smallest
+    ceil(ceil(B / 16 nt) / 256) * nt, ties to the larger NT."""
+    best, best_cost = 1, None
+    for nt in range(1, (3 if save_tape else 4) + 1):
+        blocks = (B + 16 * nt - 1) // (16 * nt)
+        cost = ((blocks + 255) // 256) * nt
+        if best_cost is None or cost <= best_cost:
+            best, best_cost = nt, cost
+    return best
+
+
+def lstm_geom(H, obs, B, save_tape, nt_env=None):
+    """csrc/hode_lstm.hip:82-124 lstm_geom -> (Hp, TPW, fTPW, fNW, NT): Hp the next compiled size, TPW = Hp / 16; the
+    forward runs fNW = 4 waves of TPW tiles for TPW <= 5, else 8 waves of TPW / 2 (csrc/hode_lstm_tpw.hip:18-19); NT from
+    choose_nt, the HODE_LSTM_NT override inside the same bound (:96-99), then the staging clamp 16 NT obs <= 5120 (:110)."""
+    Hp = next(v for v in LSTM_SIZES if H <= v)
+    tpw = Hp // 16
+    fnw = 4 if tpw <= 5 else 8
+    nt = choose_nt(B, save_tape)
+    if nt_env is not None and 1 <= nt_env <= (3 if save_tape else 4):
+        nt = nt_env
+    while nt > 1 and 16 * nt * obs > 5120:
+        nt -= 1
+    return Hp, tpw, 4 * tpw // fnw, fnw, nt
+
+
+def lstm_kernels(H, obs, B, save_tape, nt_env=None):
+    """hode_lstm_fwd (csrc/hode_lstm.hip:171 lstm_pack_kernel, then csrc/hode_lstm_tpw.hip:33-35
+    lstm_fwd_kernel<NT, fTPW, fNW, VEC4 = obs % 4 == 0>); with the tape (hode.lstm.lstm_encode) also hode_lstm_bwd
+    (csrc/hode_lstm.hip:219 lstm_pack_hh_kernel, csrc/hode_lstm_tpw.hip:47-49 lstm_bwd_kernel<NT, TPW, FLAT = H == 16 TPW>)
+    and hode_lstm_fill_operand (csrc/hode_lstm.hip:270-276 lstm_fill_operand_kernel<VEC4>: obs % 4 == 0 and 16-byte
+    aligned x / mask / h_prev, which fresh tensors are)."""
+    _, tpw, ftpw, fnw, nt = lstm_geom(H, obs, B, save_tape, nt_env)
+    vec4 = _b(obs % 4 == 0)
+    out = ["hode::lstm_pack_kernel", "hode::lstm_fwd_kernel<%d, %d, %d, %s>" % (nt, ftpw, fnw, vec4)]
+    if save_tape:
+        out += ["hode::lstm_pack_hh_kernel", "hode::lstm_bwd_kernel<%d, %d, %s>" % (nt, tpw, _b(H == 16 * tpw)),
+                "hode::lstm_fill_operand_kernel<%s>" % vec4]
+    return out
+
+
+def lstm_workspace_bytes(T, B, I, H, obs, save_tape, nt_env=None):
+    """csrc/hode_lstm.hip:152-158 hode_lstm_workspace_bytes from the restated geometry: [packed W (4 KQ4 TPW 64 4 floats,
+    Kq = ceil((I + Hp + 1) / 4), KQ4 = ceil(Kq / 4)) | packed W_hh^T | tape (T nblk 4 TPW NT 5 64 floats)], 256-aligned."""
+    Hp, tpw, _, _, nt = lstm_geom(H, obs, B, save_tape, nt_env)
+    al = lambda x: (x + 255) // 256 * 256  # noqa: E731
+    kq = (I + Hp + 1 + 3) // 4
+    kq4 = (kq + 3) // 4
+    # csrc/hode_lstm.hip:113-115: the LDS bound of the launched (clamped) tile, 0 = unsupported
+    if 2 * 4 * kq * (16 * nt + (16 if (16 * nt) % 32 == 0 else 0)) * 4 > 160 * 1024:
+        return 0
+    n = al(4 * kq4 * tpw * 64 * 4 * 4)
+    if save_tape:
+        nblk = (B + 16 * nt - 1) // (16 * nt)
+        n += al(4 * tpw * 4 * ((tpw + 3) // 4) * 64 * 4 * 4) + al(T * nblk * 4 * tpw * nt * 5 * 64 * 4)
+    return n
+
+
+def readout_mf(latent, obs, valu=False):
+    """csrc/hode_readout.hip:292-295 readout_mf: the matrix-core kernel for (12, 48 < obs <= 80) and (8, 32 < obs <= 48),
+    unless HODE_READOUT_VALU is set."""
+    if valu:
+        return False
+    return (latent == 12 and 48 < obs <= 80) or (latent == 8 and 32 < obs <= 48)
+
+
+def readout_kernels(latent, obs, grad, valu=False):
+    """csrc/hode_readout.hip:328-351 hode_readout_sse: readout_mf_kernel<12, 5, GRAD> / <8, 3, GRAD> or
+    readout_sse_kernel<D, GRAD> (GRAD = grad_h given), then readout_fold_kernel (grid P with the gradient, 1 without)."""
+    g = _b(grad)
+    if readout_mf(latent, obs, valu):
+        k = "hode::readout_mf_kernel<%s, %s>" % ("12, 5" if latent == 12 else "8, 3", g)
+    else:
+        k = "hode::readout_sse_kernel<%d, %s>" % (latent, g)
+    return [k, "hode::readout_fold_kernel"]
+
+
+def readout_waves(rows, obs, latent, valu=False):
+    """csrc/hode_readout.hip:297-301 readout_waves: 16 rows per wave-iteration on the matrix cores, 64 / (obs / 4) on the
+    lanes; at most 2048 waves."""
+    rpi = 16 if readout_mf(latent, obs, valu) else 64 // (obs // 4)
+    return max(1, min((rows + rpi - 1) // rpi, 2048))
+
+
+def readout_mlp_kernels(latent, grad):
+    """csrc/hode_readout_mlp.hip:326-334: DL = 20 if latent == 20 else 4; readout_mlp_kernel<DL, 24, GRAD> and
+    readout_mlp_fold_kernel<DL, 24>."""
+    dl = 20 if latent == 20 else 4
+    return ["hode::readout_mlp_kernel<%d, 24, %s>" % (dl, _b(grad)), "hode::readout_mlp_fold_kernel<%d, 24>" % dl]
 
 
 # ---------------------------------------------------------------------------------------------- Roche rhs bodies
@@ -360,10 +505,142 @@ def _dopri5_cases():
     return out
 
 
+NEURAL_STEP = 0.375  # fixed-grid step of the NeuralODE cases: 3/8, so t0 + dt/3 is a representable fp32 (and fp64) stage time
+
+
+def substantive(case):
+    """A case where the kernel's arithmetic really runs: T >= 3 (at least two steps / recurrences: the LSTM's W_hh product
+    multiplies the zero initial state at the first one) and a batch of more than one full 16-patient tile with a ragged
+    last one.  The guard requires every instantiation of the NeuralODE, LSTM and readout families to be reached by one;
+    T = 1 and B = 1 entries come on top."""
+    return case["T"] >= 3 and case["B"] > 16 and case["B"] % 16 != 0
+
+
+def _neural_cases():
+    """Every matrix-core (D, method) with the on-chip and the tape-writing backward, every lane-layout (D, method), each at
+    T = 6 on a ragged batch (B in {65, 100, 37, 129}: ragged against 16 and 64; 65 is one past a lane wave); perturb and the
+    dose list (n_dose 0, 1, 3 on the grid) cycle.  Extra: two equal dose times ("dup": the impulse counts twice), a dose time
+    on the rk4 1/3 stage ("third"), and the degenerate B = 1 and T = 1 (no step) calls of each layout."""
+    out, i = [], 0
+    for D in (4, 6, 8, 10, 12, 14):
+        for method in ("euler", "midpoint", "rk4"):
+            for onchip in (True, False):
+                out.append(dict(family="neural", D=D, method=method, layout="mf", onchip=onchip, B=(65, 100, 37, 129)[i % 4],
+                                T=6, perturb=bool((i // 2) % 2), n_dose=(0, 1, 3)[(i + i // 3) % 3], dose="grid"))
+                i += 1
+    for D in (6, 8, 12):
+        for method in ("euler", "midpoint", "rk4"):
+            out.append(dict(family="neural", D=D, method=method, layout="lane", onchip=False, B=(65, 130, 37)[i % 3],
+                            T=6, perturb=bool(i % 2), n_dose=(0, 1, 3)[i % 3], dose="grid"))
+            i += 1
+    for D, layout, onchip, method in ((14, "mf", True, "rk4"), (14, "mf", False, "rk4"), (12, "lane", False, "rk4"),
+                                      (10, "mf", True, "midpoint"), (8, "lane", False, "midpoint")):
+        for dose in ("dup", "third"):
+            if dose == "third" and method != "rk4":
+                continue
+            out.append(dict(family="neural", D=D, method=method, layout=layout, onchip=onchip, B=37, T=5, perturb=False,
+                            n_dose=2, dose=dose))
+    for D, layout, onchip, method in ((4, "mf", True, "midpoint"), (14, "mf", False, "rk4"), (6, "lane", False, "euler")):
+        for B, T in ((1, 6), (37, 1), (1, 1)):
+            out.append(dict(family="neural", D=D, method=method, layout=layout, onchip=onchip, B=B, T=T, perturb=True,
+                            n_dose=1, dose="grid"))
+    return out
+
+
+def _neural_dopri5_cases():
+    """Every compiled D with the first step size detached and attached on ragged batches (17 is one past a wave); then
+    B = 1, and one output time (no accepted step: the attached backward has nothing to do and is not launched)."""
+    out = []
+    for i, D in enumerate(NEURAL_DOPRI5_DIMS):
+        for detach in (True, False):
+            out.append(dict(family="neural_dopri5", D=D, detach=detach, B=(17, 70, 33, 65, 45)[(2 * i + detach) % 5], T=14))
+    out.append(dict(family="neural_dopri5", D=12, detach=False, B=1, T=14))
+    out.append(dict(family="neural_dopri5", D=8, detach=False, B=5, T=1))
+    return out
+
+
+LSTM_OBS_VEC4, LSTM_OBS_ODD = 20, 23
+
+
+def _lstm_cases():
+    """Per padded hidden size (TPW): the tape path (lstm_encode) at NT 1, 2, 3 once with H = 16 TPW and obs % 4 != 0,
+    once with H = 16 TPW - 3 and obs % 4 == 0 -- every (NT, FLAT) backward and (NT, VEC4) forward -- and the no-tape path
+    (lstm_final_state) at NT = 4 with both obs; NT forced by HODE_LSTM_NT on a batch ragged against 16 NT, T = 3 or 4.
+    Then NT chosen by choose_nt from the batch size alone (1: B = 100; 2: 4097; 3: 8193; 4: 12289 without a tape), the
+    staging clamp (obs = 100 lowers a forced NT = 4 to 3, at the largest hidden size too), and B = 1 / T = 1 calls."""
+    out = []
+    for j, tpw in enumerate(LSTM_TPWS):
+        for nt in (1, 2, 3, 4):
+            for flat in (True, False):
+                tape = nt <= 3
+                H = 16 * tpw if flat else 16 * tpw - 3
+                obs = (LSTM_OBS_ODD if flat else LSTM_OBS_VEC4) if tape else (LSTM_OBS_VEC4 if flat else LSTM_OBS_ODD)
+                out.append(dict(family="lstm", H=H, obs=obs, B=32 * nt + 5 + j, T=3 + (j + nt + flat) % 2, tape=tape, nt=nt))
+    for B, tape in ((100, True), (4097, True), (8193, True), (100, False), (4097, False), (8193, False), (12289, False)):
+        out.append(dict(family="lstm", H=13, obs=LSTM_OBS_VEC4, B=B, T=3, tape=tape, nt=None))
+    for H in (40, 150):
+        out.append(dict(family="lstm", H=H, obs=100, B=150, T=3, tape=False, nt=4))
+    for H, tape, nt in ((160, True, 3), (64, False, 4), (13, True, None)):
+        for B, T in ((1, 3), (37, 1), (1, 1)):
+            out.append(dict(family="lstm", H=H, obs=LSTM_OBS_ODD, B=B, T=T, tape=tape, nt=nt))
+    return out
+
+
+def _readout_cases():
+    """Each latent dimension of the lane kernel, both sides of every readout_mf window edge (D 12: 48 | 52, 80 | 84; D 8:
+    32 | 36, 48 | 52), the window with HODE_READOUT_VALU, row counts at the 2048-wave cap; the MLP readout at both DL;
+    then a single row.  Every case runs the call with and without the gradient (GRAD = true / false)."""
+    out = []
+    for D, obs, T, B in ((4, 20, 3, 21), (4, 128, 3, 33), (6, 20, 4, 17), (6, 92, 3, 21), (8, 32, 3, 19), (8, 36, 3, 23),
+                         (8, 48, 4, 31), (8, 52, 3, 27), (12, 48, 3, 23), (12, 52, 3, 19), (12, 80, 3, 21), (12, 84, 3, 25),
+                         (12, 80, 130, 257), (4, 20, 100, 257)):
+        out.append(dict(family="readout", D=D, obs=obs, T=T, B=B, valu=False))
+    out.append(dict(family="readout", D=12, obs=64, T=3, B=29, valu=True))
+    out.append(dict(family="readout", D=8, obs=40, T=3, B=29, valu=True))
+    out.append(dict(family="readout", D=8, obs=44, T=1, B=1, valu=False))
+    for D, T, B in ((20, 7, 33), (4, 6, 17), (4, 96, 257), (20, 1, 1)):
+        out.append(dict(family="readout_mlp", D=D, obs=24, T=T, B=B))
+    return out
+
+
+NEURAL_DIMS = (4, 6, 8, 10, 12, 14)  # csrc/hode_neural_mf.hip:220-227 launch_neural_mf (check_neural: even, 4..14)
+NEURAL_LANE_DIMS = (6, 8, 12)        # csrc/hode_neural.hip:360-368
+READOUT_LATENT = (4, 6, 8, 12)       # csrc/hode_readout.hip:340-345
+NEW_FAMILIES = ("neural", "neural_dopri5", "lstm", "readout", "readout_mlp")  # CASES families of the kernels below
+
+
+def instantiations():
+    """Every name the NeuralODE, LSTM and readout rules above can produce, over the domains they restate (dimensions,
+    methods, padded sizes, NT, flags): the guard compares it with the compiled symbols of these families."""
+    out = set()
+    for m in METHODS.values():
+        for D in NEURAL_DIMS:
+            out.update(neural_fixed(D, m, None, True) + neural_fixed(D, m, None, False))
+        for D in NEURAL_LANE_DIMS:
+            out.update(neural_fixed(D, m, "t"))
+    for D in NEURAL_DOPRI5_DIMS:
+        out.update(neural_dopri5_kernels(D, 1, False))
+    for tpw in LSTM_TPWS:
+        fnw = 4 if tpw <= 5 else 8
+        for nt in (1, 2, 3, 4):
+            for v in (True, False):
+                out.add("hode::lstm_fwd_kernel<%d, %d, %d, %s>" % (nt, 4 * tpw // fnw, fnw, _b(v)))
+                if nt <= 3:
+                    out.add("hode::lstm_bwd_kernel<%d, %d, %s>" % (nt, tpw, _b(v)))
+    out.update(["hode::lstm_pack_kernel", "hode::lstm_pack_hh_kernel", "hode::lstm_fill_operand_kernel<true>",
+                "hode::lstm_fill_operand_kernel<false>"])
+    for g in (True, False):
+        for D in READOUT_LATENT:
+            out.update(readout_kernels(D, 4, g))
+        out.update(readout_kernels(12, 64, g) + readout_kernels(8, 40, g))
+        out.update(readout_mlp_kernels(20, g) + readout_mlp_kernels(4, g))
+    return out
+
 ROCHE_N, ROCHE_T = 77, 8   # ragged batch (not a multiple of 16, 48 or 64), short grid
 DOPRI5_N, DOPRI5_T = 21, 10
 
-CASES = _seqdec_cases() + _neural_real_cases() + _real_cases() + _roche_cases() + _dopri5_cases()
+CASES = (_seqdec_cases() + _neural_real_cases() + _real_cases() + _roche_cases() + _dopri5_cases() + _neural_cases()
+         + _neural_dopri5_cases() + _lstm_cases() + _readout_cases())
 
 
 def kernels(case):
@@ -380,6 +657,17 @@ def kernels(case):
                            case["tape"], ROCHE_T, ROCHE_N)
     if f == "dopri5":
         return dopri5_kernels(case["D"], case["lanes"], case["ablate"], case["need_theta"], case["detach"], DOPRI5_N)
+    if f == "neural":
+        return neural_fixed(case["D"], METHODS[case["method"]], "t" if case["layout"] == "lane" else None, case["onchip"])
+    if f == "neural_dopri5":
+        return neural_dopri5_kernels(case["D"], case["T"] - 1, case["detach"])
+    if f == "lstm":
+        return lstm_kernels(case["H"], case["obs"], case["B"], case["tape"], case["nt"])
+    if f == "readout":
+        return readout_kernels(case["D"], case["obs"], True, case["valu"]) + readout_kernels(case["D"], case["obs"], False,
+                                                                                           case["valu"])[:1]
+    if f == "readout_mlp":
+        return readout_mlp_kernels(case["D"], True) + readout_mlp_kernels(case["D"], False)[:1]
     raise ValueError(f)
 
 
@@ -410,3 +698,13 @@ for _D in (8, 12):
 # (instantiation, body) pairs of reachable instantiations that no dispatch of the library reaches ((name, body) -> reason).
 # Empty: ablate instantiations hold no general body (bodies()), and every other pair has a call.
 UNREACHABLE_BODIES = {}
+
+# kernel symbols of the library outside FAMILIES -> the test that checks them against a float64 reference
+# (tests/test_kernel_variant_coverage.py: every `.kd` symbol of the build is in FAMILIES or here)
+OTHER_KERNELS = {
+    "hode::crps_kernel": "tests/test_hip_crps.py::test_linear_readout_crps_vs_oracle",
+    "hode::mc_kl_exp_kernel": "tests/test_hip_mckl.py::test_fused_mc_kl_matches_reference_loop",
+    # the weight / theta gradient fold behind the Roche lane-kernel backward (csrc/hode_api.hip:255), the Roche dopri5
+    # backward (csrc/hode_dopri5.hip:264, :274) and hode_real.hip (:412): every lane / dopri5 / real_kernel case runs it
+    "hode::fold_partials_kernel": "tests/test_hip_kernel_variants.py::test_roche_fixed_grid",
+}

@@ -467,3 +467,357 @@ def test_dopri5_backward(case, record_property):
         assert len(tape2["t"]) == len(tape["t"])
         for k in got:
             assert _rel(got[k], at2[k]) <= HILL_ULP_TOL, (k, _rel(got[k], at2[k]))
+
+
+# ------------------------------------------------------------------------------------------ NeuralODE rhs, fixed grid
+def _neural_problem(case):
+    """Inputs of one fixed-grid NeuralODE case: grid t = k * 3/8 (exact fp32), dose times (B, K) as fp32 values the kernel
+    compares exactly -- on the grid ("grid"), two equal ones ("dup": the impulse counts twice) or on the rk4 1/3 stage
+    t0 + dt/3 ("third") -- and an fp64 NeuralRHS on the same values."""
+    from oracle.rhs import NeuralRHS
+    D, B, T, K = case["D"], case["B"], case["T"], case["n_dose"]
+    gen = torch.Generator().manual_seed(D * 1000 + B + 7 * T)
+    torch.manual_seed(D + B)
+    f = NeuralRHS(D, kv.NEURAL_STEP)
+    with torch.no_grad():
+        f.ml_net[2].weight.mul_(2.0)
+    t = torch.arange(T, dtype=torch.float32) * kv.NEURAL_STEP
+    y0 = torch.randn(B, D, generator=gen) * 0.5
+    dosage = 0.5 + torch.rand(B, generator=gen) * 2
+    idx = torch.randint(0, T, (B, K), generator=gen)
+    times = t[idx] if K else torch.zeros(B, 0)
+    if case["dose"] == "dup":
+        times[:, 1] = times[:, 0]
+    elif case["dose"] == "third":
+        step = torch.arange(B) % (T - 1)
+        times[:, 0] = t[step] + 0.125
+        # the fp32 stage time of the kernel (add_rn(t0, mul_rn(dt, 1/3f))) and the oracle's fp64 t0 + dt * (1/3) both hit it
+        t0, dt = t[step], t[step + 1] - t[step]
+        s32 = t0 + dt * torch.tensor(1.0 / 3.0, dtype=torch.float32)
+        assert torch.equal(s32, times[:, 0])
+        assert torch.equal(t0.double() + dt.double() * (1 / 3), times[:, 0].double())
+    cot = torch.randn(T, B, D, generator=gen)
+    return dict(f=f, t=t, y0=y0, dosage=dosage, times=times, cot=cot)
+
+
+def _neural_ref(p, method, perturb):
+    from oracle.solvers import odeint as oracle_odeint
+    f64 = copy.deepcopy(p["f"]).double()
+    f64.dosage, f64.times = p["dosage"].double(), p["times"].double()
+    y64 = p["y0"].double().requires_grad_(True)
+    h = oracle_odeint(f64, y64, p["t"].double(), method=method, options={"perturb": perturb})
+    (h * p["cot"].double()).sum().backward()
+    n = f64.ml_net
+    g = [q.grad if q.grad is not None else torch.zeros_like(q) for q in (n[0].weight, n[0].bias, n[2].weight, n[2].bias)]
+    return dict(h=h.detach(), gy0=y64.grad, gw1=g[0], gb1=g[1], gw2=g[2], gb2=g[3])  # T = 1: no step, zero weight gradients
+
+
+def _neural_params(p, dev):
+    n = p["f"].ml_net
+    return [x.detach().clone().to(dev).requires_grad_(True) for x in (n[0].weight, n[0].bias, n[2].weight, n[2].bias)]
+
+
+def _neural_gpu(p, method, perturb, dev):
+    """hode.neural.neural_solve + autograd: the on-chip backward (mf) or the tape backward of the lane layout."""
+    from hode.neural import neural_solve
+    prm = _neural_params(p, dev)
+    y0 = p["y0"].to(dev).requires_grad_(True)
+    h = neural_solve(y0, *prm, p["t"].to(dev), p["dosage"].to(dev), p["times"].to(dev), method=method, perturb=perturb)
+    (h * p["cot"].to(dev)).sum().backward()
+    torch.cuda.synchronize()
+    return dict(h=h.detach(), gy0=y0.grad, gw1=prm[0].grad, gb1=prm[1].grad, gw2=prm[2].grad, gb2=prm[3].grad)
+
+
+def _neural_gpu_tape_backward(p, method, perturb, dev):
+    """The matrix-core backward without grad_w1 (C ABI): neural_mf_bwd_kernel<D, M, false> writes the operand tapes, which
+    hode.neural.contract_tape contracts exactly as the lane layout's backward does."""
+    import hode
+    from hode import _lib as L
+    from hode.neural import _desc, contract_tape, neural_solve
+    lib = hode.lib()
+    w1, b1, w2, b2 = (x.detach() for x in _neural_params(p, dev))
+    y0, t, dos, tms = p["y0"].to(dev), p["t"].to(dev), p["dosage"].to(dev), p["times"].to(dev).contiguous()
+    h = neural_solve(y0, w1, b1, w2, b2, t, dos, tms, method=method, perturb=perturb).detach()
+    gh = p["cot"].to(dev).contiguous()
+    gy0 = torch.empty_like(y0)
+    d = _desc(y0, t, dos, tms, w1, b1, w2, b2, h, L.METHODS[method], perturb)
+    d.grad_h, d.grad_y0 = gh.data_ptr(), gy0.data_ptr()
+    n = lib.hode_workspace_bytes(d, L.WS_RK_BWD)
+    ws = torch.empty(max(n, 4), device=dev, dtype=torch.uint8)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), n
+    L.check(lib.hode_rk_bwd(d, torch.cuda.current_stream().cuda_stream), "hode_rk_bwd[neural, tape]")
+    T, B, D = h.shape
+    gw1, gb1, gw2, gb2 = contract_tape(ws, d, T, B, D, L.METHODS[method])
+    torch.cuda.synchronize()
+    return dict(h=h, gy0=gy0, gw1=gw1, gb1=gb1, gw2=gw2, gb2=gb2)
+
+
+NEURAL_GRADS = ("gy0", "gw1", "gb1", "gw2", "gb2")
+
+
+@pytest.mark.parametrize("case", _family("neural"), ids=kv.case_id)
+def test_neural_fixed_grid(case, monkeypatch, record_property):
+    """neural_mf_* (on-chip and tape-writing backward) and the lane layout against oracle.rhs.NeuralRHS in fp64 with
+    oracle.solvers.odeint, perturb included: trajectory 2e-5 (1 + max|h|), every gradient rel-L2 1e-4.  The tape backward is
+    also compared with the on-chip backward on the same inputs (_tape_same_as_onchip)."""
+    dev = _dev()
+    if case["layout"] == "lane":
+        monkeypatch.setenv("HODE_NEURAL_LAYOUT", "t")
+    else:
+        monkeypatch.delenv("HODE_NEURAL_LAYOUT", raising=False)
+    method, perturb = case["method"], case["perturb"]
+    p = _neural_problem(case)
+    ref = _neural_ref(p, method, perturb)
+    if case["dose"] == "third":  # the 1/3-stage impulse is part of the problem: one ulp later it does not fire
+        q = dict(p, times=p["times"].clone())
+        q["times"][:, 0] = torch.nextafter(q["times"][:, 0], torch.tensor(1e9))
+        assert (_neural_ref(q, method, perturb)["h"] - ref["h"]).abs().max() > 1e-3
+    got = _neural_gpu_tape_backward(p, method, perturb, dev) if not case["onchip"] and case["layout"] == "mf" \
+        else _neural_gpu(p, method, perturb, dev)
+    assert torch.equal(got["h"][0].cpu(), p["y0"])
+    _traj_ok(got["h"], ref["h"])
+    record_property("err_h", (got["h"].double().cpu() - ref["h"]).abs().max().item() / (1 + ref["h"].abs().max().item()))
+    for k in NEURAL_GRADS:
+        err = _rel(got[k], ref[k]) if float(ref[k].abs().max()) > 0 else float(got[k].abs().max())
+        record_property("err_" + k, err)
+        assert err <= 1e-4, (k, err)
+    if not case["onchip"] and case["layout"] == "mf":
+        _tape_same_as_onchip(got, _neural_gpu(p, method, perturb, dev), method, record_property)
+
+
+def _tape_same_as_onchip(tape, onchip, method, record_property):
+    """neural_mf_bwd_kernel<D, M, false> against <D, M, true> on the same inputs; h comes from the same forward.  grad_y0
+    is bit-identical for euler and midpoint.  For rk4 the on-chip variant keeps one stage's activations and recomputes the
+    others, and the compiler contracts the four-stage adjoint into different fmas than in the tape variant: grad_y0 moves by
+    an ulp or two (rel-L2 <= 7.5e-8 measured over the table).  The weight gradients are the same sums in a different order
+    -- BLAS GEMMs over (instance, patient) against per-wave MFMA outer products folded in wave order -- (<= 4.0e-7
+    measured).  Both are held to rel-L2 <= 1e-6 (_same_as_with_theta's bound): far below the 1e-4 fp64 tolerance, far above
+    the reordering noise."""
+    assert torch.equal(tape["h"], onchip["h"])
+    e = _rel(tape["gy0"], onchip["gy0"])
+    record_property("tape_vs_onchip_gy0", e)
+    _same_as_with_theta(tape["gy0"], onchip["gy0"], method != "rk4", "gy0")
+    for k in NEURAL_GRADS[1:]:
+        e = _rel(tape[k], onchip[k]) if float(onchip[k].abs().max()) > 0 else float(tape[k].abs().max())
+        record_property("tape_vs_onchip_" + k, e)
+        assert e <= 1e-6, (k, e)
+
+
+# ------------------------------------------------------------------------------------------------- NeuralODE dopri5
+@pytest.mark.parametrize("case", _family("neural_dopri5"), ids=kv.case_id)
+def test_neural_dopri5(case, record_property):
+    """ndp_fwd_kernel (all three phases), ndp_bwd_kernel and, with the first step size attached, ndp_initbwd_kernel against
+    the oracle's dopri5 step algebra replayed in fp64 along the run's own tape (oracle.solvers.odeint_dopri5_replay):
+    trajectory 5e-6 (1 + max|h|), every gradient rel-L2 1e-4 (test_hip_neural's replay check)."""
+    from hode import adaptive
+    from oracle.solvers import odeint_dopri5_replay
+    from test_hip_neural import _neural_case, _neural_hip_dopri5
+    dev = _dev()
+    D, B, T = case["D"], case["B"], case["T"]
+    rtol, atol = 1e-6, 1e-8
+    inp, f = _neural_case(B, max(T, 2), D, seed=D + B)
+    if T == 1:  # one output time: no step, the attached backward is not launched
+        inp = {"z0": inp["z0"], "actions": inp["actions"][:1] * 0, "t": inp["t"][:1]}
+        f.set_action(inp["actions"])
+    cot = torch.randn(T, B, D, generator=torch.Generator().manual_seed(D))
+    adaptive.keep_workspace = True
+    try:
+        got = _neural_hip_dopri5(inp, f, dev, cot, rtol, atol, detach=case["detach"])
+        tape = adaptive.read_tape()
+    finally:
+        adaptive.keep_workspace = False
+    assert (got["stats"]["n_accepted"] > 0) == (T > 1)
+    first = (not case["detach"]) and T > 1 and bool(tape["init"]["first_accepted"])
+    f64 = copy.deepcopy(f).double()
+    f64.dosage, f64.times = f.dosage.double(), f.times.double()
+    y64 = inp["z0"].double().requires_grad_(True)
+    pairs = list(zip(tape["t"], tape["dt"])) if T > 1 else []
+    hr = odeint_dopri5_replay(f64, y64, inp["t"].double(), rtol, atol, pairs, first)
+    (hr * cot.double()).sum().backward()
+    err = (got["h"].double() - hr.detach()).abs().max().item()
+    record_property("err_h", err / (1 + hr.abs().max().item()))
+    assert err <= 5e-6 * (1 + hr.abs().max().item()), err
+    n = f64.ml_net
+    for k, a, b in zip(NEURAL_GRADS, got["g"], [y64.grad, n[0].weight.grad, n[0].bias.grad, n[2].weight.grad, n[2].bias.grad]):
+        if T == 1:
+            assert (torch.equal(a, cot[0]) if k == "gy0" else float(a.abs().max()) == 0.0), k
+            continue
+        e = _rel(a, b)
+        record_property("err_" + k, e)
+        assert e <= 1e-4, (k, case["detach"], e)
+
+
+# ------------------------------------------------------------------------------------------------------- LSTM encoder
+def _lstm_problem(case):
+    from oracle.encoder import EncoderLSTMOracle
+    H, obs, B, T = case["H"], case["obs"], case["B"], case["T"]
+    gen = torch.Generator().manual_seed(H * 100 + obs + B)
+    torch.manual_seed(H + obs)
+    enc = EncoderLSTMOracle(obs + 1, H, 12)
+    with torch.no_grad():
+        for prm in enc.lstm.parameters():
+            prm.mul_(1.5)
+    x = torch.randn(T, B, obs, generator=gen)
+    a = torch.rand(T, B, 1, generator=gen) * (torch.rand(T, B, 1, generator=gen) < 0.3).float()
+    m = (torch.rand(T, B, obs, generator=gen) < 0.5).float()
+    cot = torch.randn(B, H, generator=gen)
+    return enc, x, a, m, cot
+
+
+def _lstm_fwd_tape(x, a, m, w, dev):
+    """hode_lstm_fwd with save_tape = 1 (the forward lstm_encode runs), for its final c."""
+    import hode
+    from hode import _lib as L
+    from hode.lstm import _desc
+    lib = hode.lib()
+    B, H = x.shape[1], w[1].shape[1]
+    h = torch.empty((B, H), device=dev)
+    c = torch.empty((B, H), device=dev)
+    d = _desc(x, a, m, *w, True, True)
+    d.h_out, d.c_out = h.data_ptr(), c.data_ptr()
+    n = lib.hode_lstm_workspace_bytes(d)
+    assert n > 0
+    ws = torch.empty(n, device=dev, dtype=torch.uint8)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), n
+    L.check(lib.hode_lstm_fwd(d, torch.cuda.current_stream().cuda_stream), "hode_lstm_fwd")
+    torch.cuda.synchronize()
+    return h, c
+
+
+def _lstm_fill_operand_ok(x, a, m, w, dev):
+    """hode_lstm_fill_operand writes h_prev[t][b][0:obs] = x * mask and nothing else: exact, the rest stays NaN."""
+    import hode
+    from hode import _lib as L
+    from hode.lstm import _desc
+    lib = hode.lib()
+    T, B, obs = x.shape
+    H = w[1].shape[1]
+    W = (obs + 1 + H + 1 + 3) // 4 * 4
+    hp = torch.full((T, B, W), float("nan"), device=dev)
+    d = _desc(x, a, m, *w, True, True)
+    dummy = torch.empty(1, device=dev)
+    d.h_out, d.c_out, d.h_prev = dummy.data_ptr(), dummy.data_ptr(), hp.data_ptr()
+    L.check(lib.hode_lstm_fill_operand(d, torch.cuda.current_stream().cuda_stream), "hode_lstm_fill_operand")
+    torch.cuda.synchronize()
+    assert torch.equal(hp[..., :obs], x * m)
+    assert torch.isnan(hp[..., obs:]).all()
+
+
+@pytest.mark.parametrize("case", _family("lstm"), ids=kv.case_id)
+def test_lstm(case, monkeypatch, record_property):
+    """lstm_fwd_kernel / lstm_bwd_kernel / lstm_fill_operand_kernel against oracle.encoder.EncoderLSTMOracle in fp64: final h
+    to 2e-5 and c to 5e-5 (absolute, test_hip_lstm's bounds), grad_w_ih / grad_w_hh / grad_b_ih / grad_b_hh of sum(h * cot)
+    rel-L2 1e-4.  Tape cases go through hode.lstm.lstm_encode (and the ABI forward for c), the others through
+    lstm_final_state; NT from HODE_LSTM_NT where the case forces it, else from the batch size."""
+    from hode.lstm import lstm_encode, lstm_final_state
+    dev = _dev()
+    if case["nt"] is None:
+        monkeypatch.delenv("HODE_LSTM_NT", raising=False)
+    else:
+        monkeypatch.setenv("HODE_LSTM_NT", str(case["nt"]))
+    enc, x, a, m, cot = _lstm_problem(case)
+    e64 = copy.deepcopy(enc).double()
+    h64, c64 = e64.final_hidden(x.double(), a.double(), m.double())
+    (h64 * cot.double()).sum().backward()
+    p = enc.lstm
+    w = [q.detach().to(dev) for q in (p.weight_ih_l0, p.weight_hh_l0, p.bias_ih_l0, p.bias_hh_l0)]
+    xd, ad, md = x.to(dev), a.to(dev), m.to(dev)
+    if case["tape"]:
+        h, c = _lstm_fwd_tape(xd, ad, md, w, dev)
+        wg = [q.clone().requires_grad_(True) for q in w]
+        he = lstm_encode(xd, ad, md, *wg, reverse=True)
+        assert torch.equal(he.detach(), h)
+        (he * cot.to(dev)).sum().backward()
+        q64 = e64.lstm
+        for name, g, r in zip(("w_ih", "w_hh", "b_ih", "b_hh"), wg,
+                              (q64.weight_ih_l0, q64.weight_hh_l0, q64.bias_ih_l0, q64.bias_hh_l0)):
+            e = _rel(g.grad, r.grad)
+            record_property("err_g" + name, e)
+            assert e <= 1e-4, (name, e)
+        _lstm_fill_operand_ok(xd, ad, md, w, dev)
+    else:
+        h, c = lstm_final_state(xd, ad, md, *w, reverse=True)
+    eh = (h.double().cpu() - h64.detach()).abs().max().item()
+    ec = (c.double().cpu() - c64.detach()).abs().max().item()
+    record_property("err_h", eh)
+    record_property("err_c", ec)
+    assert eh <= 2e-5 and ec <= 5e-5, (eh, ec)
+
+
+# ------------------------------------------------------------------------------------------------------------ readouts
+def _lik_same(lik, lik0, record_property):
+    """The loss from the GRAD = false launch against the GRAD = true launch on the same inputs: bit-identical (the loss
+    partials are formed by the same code in both instantiations and folded by the same kernel in the same order)."""
+    record_property("lik_grad_vs_nograd", abs(lik0 - lik) / abs(lik))
+    assert lik0 == lik, (lik0, lik)
+
+
+@pytest.mark.parametrize("case", _family("readout"), ids=kv.case_id)
+def test_readout(case, monkeypatch, record_property):
+    """readout_sse_kernel / readout_mf_kernel (GRAD true and false) + readout_fold_kernel against the fp64 torch expression
+    (test_hip_readout's bounds: loss rel 2e-5, gradients rel-L2 2e-5)."""
+    from hode.readout import masked_sse_readout
+    dev = _dev()
+    if case["valu"]:
+        monkeypatch.setenv("HODE_READOUT_VALU", "1")
+    else:
+        monkeypatch.delenv("HODE_READOUT_VALU", raising=False)
+    D, obs, T, B = case["D"], case["obs"], case["T"], case["B"]
+    gen = torch.Generator().manual_seed(D * 1000 + obs + B)
+    torch.manual_seed(obs + T)
+    h = torch.randn(T, B, D, generator=gen)
+    x = torch.randn(T, B, obs, generator=gen)
+    m = torch.rand(T, B, obs, generator=gen) * (torch.rand(T, B, obs, generator=gen) < 0.6).float()
+    lin = torch.nn.Linear(D, obs)
+    hr = h.clone().double().requires_grad_(True)
+    w64, b64 = lin.weight.detach().double().requires_grad_(True), lin.bias.detach().double().requires_grad_(True)
+    ref = torch.sum((x.double() - (hr @ w64.t() + b64)) ** 2 * m.double()) / B
+    ref.backward()
+    hg = h.to(dev).requires_grad_(True)
+    wg, bg = lin.weight.detach().to(dev).requires_grad_(True), lin.bias.detach().to(dev).requires_grad_(True)
+    lik = masked_sse_readout(hg, x.to(dev), m.to(dev), wg, bg)
+    lik.backward()
+    with torch.no_grad():
+        lik0 = masked_sse_readout(hg.detach(), x.to(dev), m.to(dev), wg.detach(), bg.detach())
+    e = abs(lik.item() - ref.item()) / abs(ref.item())
+    record_property("err_lik", e)
+    assert e <= 2e-5, e
+    for k, g, want in (("gh", hg.grad, hr.grad), ("gw", wg.grad, w64.grad), ("gb", bg.grad, b64.grad)):
+        e = _rel(g, want)
+        record_property("err_" + k, e)
+        assert e <= 2e-5, (k, e)
+    _lik_same(lik.item(), lik0.item(), record_property)
+
+
+@pytest.mark.parametrize("case", _family("readout_mlp"), ids=kv.case_id)
+def test_readout_mlp(case, record_property):
+    """readout_mlp_kernel<DL, 24, GRAD true / false> + readout_mlp_fold_kernel against the fp64 torch expression
+    (test_hip_readout's bounds: loss rel 2e-5, gradients rel-L2 3e-5)."""
+    from hode.readout import masked_sse_readout_mlp
+    dev = _dev()
+    D, obs, T, B = case["D"], case["obs"], case["T"], case["B"]
+    gen = torch.Generator().manual_seed(D * 1000 + B + T)
+    torch.manual_seed(D + 3 * T)
+    h = torch.randn(T, B, D, generator=gen)
+    x = torch.randn(T, B, obs, generator=gen)
+    m = (torch.rand(T, B, obs, generator=gen) < 0.5).float()
+    net = torch.nn.Sequential(torch.nn.Linear(D, D + 1), torch.nn.ELU(), torch.nn.Linear(D + 1, obs))
+    net64 = copy.deepcopy(net).double()
+    hr = h.clone().double().requires_grad_(True)
+    ref = torch.sum((x.double() - net64(hr)) ** 2 * m.double()) / B
+    ref.backward()
+    hg = h.to(dev).requires_grad_(True)
+    prm = [q.detach().clone().to(dev).requires_grad_(True) for q in (net[0].weight, net[0].bias, net[2].weight, net[2].bias)]
+    lik = masked_sse_readout_mlp(hg, x.to(dev), m.to(dev), *prm)
+    lik.backward()
+    with torch.no_grad():
+        lik0 = masked_sse_readout_mlp(h.to(dev), x.to(dev), m.to(dev), *[q.detach() for q in prm])
+    e = abs(lik.item() - ref.item()) / abs(ref.item())
+    record_property("err_lik", e)
+    assert e <= 2e-5, e
+    wants = (hr.grad, net64[0].weight.grad, net64[0].bias.grad, net64[2].weight.grad, net64[2].bias.grad)
+    for k, g, want in zip(("gh", "gw1", "gb1", "gw2", "gb2"), [hg.grad] + [q.grad for q in prm], wants):
+        e = _rel(g, want)
+        record_property("err_" + k, e)
+        assert e <= 3e-5, (k, e)
+    _lik_same(lik.item(), lik0.item(), record_property)

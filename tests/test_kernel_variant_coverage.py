@@ -6,6 +6,7 @@ A new tile class, method or flag that no test reaches fails here.
 The Roche kernels branch at run time between inlined rhs bodies (kv.roche_body), which the symbols do not show: every
 (instantiation, body) pair must be reached by a case too, and the branch itself is read out of the kernel source and
 compared with kv.bodies(), so that a new body or a changed condition fails here as well."""
+import ast
 import ctypes
 import glob
 import os
@@ -24,19 +25,19 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
 @pytest.fixture(scope="module")
-def compiled():
+def all_compiled():
+    """Every kernel symbol (`.kd`) of the library's object files."""
     objs = sorted(glob.glob(os.path.join(BUILD, "*.o")))
     objs = [o for o in objs if "__" not in os.path.basename(o)]  # experiment builds (build_hip.build_variant)
     if not objs:
         pytest.skip("object files are not in the tree (library shipped pre-built)")
     from kernel_descriptor import kernel_descriptors
-    names = set()
-    for o in objs:
-        for dem, _ in kernel_descriptors(o):
-            n = kv.kernel_name(dem)
-            if kv.family(n):
-                names.add(n)
-    return names
+    return {kv.kernel_name(dem) for o in objs for dem, _ in kernel_descriptors(o)}
+
+
+@pytest.fixture(scope="module")
+def compiled(all_compiled):
+    return {n for n in all_compiled if kv.family(n)}
 
 
 def _covered():
@@ -361,3 +362,203 @@ def test_real_mf_tile_rule_matches_the_workspace_size():
     # without grad_w1 the tape layout grows with every hidden unit (both the tape kernels and the tape-writing MFMA one)
     sizes = [lib.hode_workspace_bytes(_solve_desc(L.RHS_ROCHE_REAL, 20, H), L.WS_RK_BWD) for H in (16, 17, 64, 65)]
     assert sizes == sorted(sizes) and len(set(sizes)) == 4
+
+
+# ------------------------------------------------------------------------------------------------ the whole library
+def test_every_kernel_of_the_library_is_accounted_for(all_compiled):
+    """Every kernel symbol of the build belongs to a covered family (FAMILIES) or is named in kv.OTHER_KERNELS with the
+    test that checks it against a float64 reference: a new __global__ anywhere fails here until it is one or the other."""
+    stray = sorted(n for n in all_compiled if not kv.family(n) and n not in kv.OTHER_KERNELS)
+    assert not stray, "kernels outside FAMILIES and OTHER_KERNELS:\n  %s" % "\n  ".join(stray)
+    assert set(kv.OTHER_KERNELS) <= all_compiled, sorted(set(kv.OTHER_KERNELS) - all_compiled)
+    assert not any(kv.family(n) for n in kv.OTHER_KERNELS)
+    covered = set(_covered())
+    for name, test in kv.OTHER_KERNELS.items():
+        assert name not in covered, name  # a case lists it: it belongs in FAMILIES
+        path, func = test.split("::")
+        tree = ast.parse(open(os.path.join(ROOT, path)).read())
+        assert func in {f.name for f in tree.body if isinstance(f, ast.FunctionDef)}, test
+
+
+def test_new_families_are_covered_by_substantive_cases(compiled):
+    """The NeuralODE, LSTM and readout instantiations in the build are exactly those the restated rules produce over their
+    domains (kv.instantiations), and each is reached by a case where its arithmetic really runs (kv.substantive: T >= 3,
+    B > 16 and ragged): a T = 1 or B = 1 entry alone does not count."""
+    fams = {kv.family(n) for c in kv.CASES if c["family"] in kv.NEW_FAMILIES for n in kv.kernels(c)}
+    have = {n for n in compiled if kv.family(n) in fams}
+    want = kv.instantiations()
+    assert have == want, (sorted(have - want), sorted(want - have))
+    real = {n for c in kv.CASES if c["family"] in kv.NEW_FAMILIES and kv.substantive(c) for n in kv.kernels(c)}
+    missing = sorted(want - real)
+    assert not missing, "instantiations reached only by T = 1 / B <= 16 cases:\n  %s" % "\n  ".join(missing)
+    for fam in kv.NEW_FAMILIES:  # and the degenerate calls are there on top
+        cs = [c for c in kv.CASES if c["family"] == fam]
+        assert any(c["B"] == 1 for c in cs) and any(c["T"] == 1 for c in cs), fam
+
+
+def test_neural_rules():
+    assert kv.neural_layout(6, "t") == "lane" and kv.neural_layout(6, "tape") == "lane" and kv.neural_layout(6, "m") == "mf"
+    assert kv.neural_layout(14) == "mf" and kv.neural_layout(4, "") == "mf"
+    with pytest.raises(AssertionError):
+        kv.neural_layout(14, "t")
+    assert kv.neural_grid(65, "mf") == 5 and kv.neural_grid(65, "lane") == 2 and kv.neural_grid(64, "lane") == 1
+    assert kv.neural_fixed(8, kv.RK4, None, False)[-1] == "hode::neural_mf_bwd_kernel<8, 2, false>"
+    assert "hode::transpose_w2_kernel" in kv.neural_fixed(8, kv.RK4, "t", True)
+    assert not any("initbwd" in n for n in kv.neural_dopri5_kernels(8, 0, False))
+    assert not any("initbwd" in n for n in kv.neural_dopri5_kernels(8, 5, True))
+    # the dose / tile edges the issue names appear somewhere in the table
+    nc = [c for c in kv.CASES if c["family"] == "neural"]
+    assert any(c["B"] % 16 and c["B"] % 64 for c in nc) and any(c["B"] == 65 and c["layout"] == "lane" for c in nc)
+    assert any(c["B"] == 1 for c in nc) and any(c["T"] == 1 for c in nc)
+    assert {c["perturb"] for c in nc} == {False, True} and {0, 1, 3} <= {c["n_dose"] for c in nc}
+    assert {c["dose"] for c in nc} == {"grid", "dup", "third"}
+    assert any(c["dose"] == "third" and c["method"] == "rk4" for c in nc)
+    assert all(c["n_dose"] >= 2 for c in nc if c["dose"] != "grid")
+
+
+def test_neural_source_pins_the_restated_rules():
+    """The lines kv.neural_layout / neural_fixed / neural_dopri5_kernels restate, as they read in the source."""
+    nh = _norm(_strip_and_expand(open(os.path.join(CSRC, "hode_neural.hip")).read()))
+    assert "if (!(env && env[0] == 't')) return launch_neural_mf(d, a, bwd, s);" in nh
+    assert "if (D != 6 && D != 8 && D != 12)" in nh
+    assert "const dim3 grid((d->batch + 63) / 64), block(64);" in nh
+    mf = _norm(_strip_and_expand(open(os.path.join(CSRC, "hode_neural_mf.hip")).read()))
+    assert "const dim3 grid((d->batch + 15) / 16), block(64); const bool onchip = bwd && d->grad_w1 != nullptr;" in mf
+    raw = open(os.path.join(CSRC, "hode_neural_dopri5.hip")).read()
+    assert "#define HODE_ND_DIMS(X) " + " ".join("X(%d)" % D for D in kv.NEURAL_DOPRI5_DIMS) + "\n" in raw
+    nd = _norm(_strip_and_expand(raw))
+    assert "if (a.n_acc > 0 && !(d->flags & HODE_FLAG_DETACH_FIRST_STEP)) {" in nd
+
+
+def test_lstm_rules():
+    """FLAT and VEC4 against an independent statement of them (the padded sizes; obs % 4), NT's bounds and its tie rule."""
+    for H in range(1, 161):
+        flat = kv.lstm_kernels(H, 20, 37, True)[3].endswith("true>")
+        assert flat == (H in kv.LSTM_SIZES), H
+    for obs in range(1, 41):
+        assert kv.lstm_kernels(16, obs, 37, True)[1].endswith("true>") == (obs % 4 == 0)
+        assert kv.lstm_kernels(16, obs, 37, True)[4].endswith("true>") == (obs % 4 == 0)
+    assert [kv.choose_nt(B, True) for B in (1, 4096, 4097, 8193, 12289)] == [1, 1, 2, 3, 2]
+    assert [kv.choose_nt(B, False) for B in (1, 4097, 8193, 12289)] == [1, 2, 3, 4]
+    assert kv.lstm_geom(40, 100, 150, False, 4)[4] == 3  # the staging clamp after the override
+    # the LDS bound is checked on the clamped tile: H = 129 .. 160 with obs = 100 at NT 4 -> 3 is supported
+    assert kv.lstm_workspace_bytes(3, 12289, 101, 150, 100, False) > 0
+    assert any(c["family"] == "lstm" and c["H"] > 128 and c["obs"] == 100 and c["nt"] == 4 for c in kv.CASES)
+    assert kv.lstm_geom(40, 20, 150, True, 4)[4] == kv.choose_nt(150, True)  # override outside the bound: ignored
+    seen = {}
+    for c in kv.CASES:
+        if c["family"] == "lstm" and c["nt"] is None:
+            seen.setdefault(kv.lstm_geom(c["H"], c["obs"], c["B"], c["tape"])[4], []).append(c)
+    assert sorted(seen) == [1, 2, 3, 4]  # each NT chosen from the batch size alone, not the override
+    lc = [c for c in kv.CASES if c["family"] == "lstm"]
+    for tpw in kv.LSTM_TPWS:
+        hs = {c["H"] % 16 == 0 for c in lc if kv.lstm_geom(c["H"], c["obs"], c["B"], c["tape"])[1] == tpw}
+        assert hs == {True, False}, tpw
+
+
+def test_lstm_source_pins_the_restated_rules():
+    src = _norm(_strip_and_expand(open(os.path.join(CSRC, "hode_lstm_tpw.hip")).read()))
+    assert "constexpr int kFwdNW = kTPW <= 5 ? 4 : 8;" in src and "constexpr int kFwdTPW = kTPW <= 5 ? kTPW : kTPW / 2;" in src
+    assert "return (a.OBS & 3) == 0 ? launch_fwd_vec<NT, true>(G, a, s) : launch_fwd_vec<NT, false>(G, a, s);" in src
+    assert "return a.H == 16 * kTPW ? launch_bwd_flat<NT, true>(G, a, s) : launch_bwd_flat<NT, false>(G, a, s);" in src
+    lh = _norm(_strip_and_expand(open(os.path.join(CSRC, "hode_lstm.hip")).read()))
+    assert "static const int kSizes[] = {%s};" % ", ".join(str(v) for v in kv.LSTM_SIZES) in lh
+    assert "const bool vec4 = (obs & 3) == 0 &&" in lh
+    import build_hip
+    assert tuple(sorted(build_hip.LSTM_TPWS)) == tuple(sorted(kv.LSTM_TPWS))
+
+
+def _lstm_desc(T, B, obs, H, tape):
+    from hode import _lib as L
+    d = L.new_lstm_desc()
+    d.seq_len, d.batch, d.input_dim, d.hidden_dim, d.obs_dim, d.save_tape = T, B, obs + 1, H, obs, int(tape)
+    return d
+
+
+def test_lstm_geometry_matches_the_workspace_size(monkeypatch):
+    """hode_lstm_workspace_bytes against kv.lstm_workspace_bytes: the packed weights depend on Hp and KQ4, the tape on NT
+    (nblk NT differs between tiles for ragged batches) -- with NT chosen by the batch size (both sides of every tie) and
+    forced by HODE_LSTM_NT, the staging clamp included."""
+    import hode
+    lib = hode.lib()
+    monkeypatch.delenv("HODE_LSTM_NT", raising=False)
+    Bs = (1, 17, 4095, 4096, 4097, 6145, 8192, 8193, 12288, 12289, 16385, 20481, 24577)
+    n = 0
+    for H in (1, 13, 16, 17, 47, 64, 65, 96, 97, 125, 128, 129, 160):
+        for obs in (1, 20, 23, 80, 100):
+            for B in Bs:
+                for tape in (True, False):
+                    got = lib.hode_lstm_workspace_bytes(_lstm_desc(3, B, obs, H, tape))
+                    assert got == kv.lstm_workspace_bytes(3, B, obs + 1, H, obs, tape), (H, obs, B, tape)
+                    n += 1
+    assert n > 1000
+    for nt in (1, 2, 3, 4):
+        monkeypatch.setenv("HODE_LSTM_NT", str(nt))
+        for B in (37, 101, 4097):
+            for obs in (20, 100):
+                got = lib.hode_lstm_workspace_bytes(_lstm_desc(2, B, obs, 40, True))
+                assert got == kv.lstm_workspace_bytes(2, B, obs + 1, 40, obs, True, nt), (nt, B, obs)
+
+
+def test_readout_rules_match_the_workspace_size(monkeypatch):
+    """hode_readout_workspace_bytes = readout_waves * (1 + obs D + obs) floats: the waves depend on whether readout_mf was
+    chosen (16 rows per wave-iteration against 64 / (obs / 4)) -- every obs at both latent dimensions with a window, with and
+    without HODE_READOUT_VALU."""
+    import hode
+    from hode import _lib as L
+    lib = hode.lib()
+    for valu in (False, True):
+        if valu:
+            monkeypatch.setenv("HODE_READOUT_VALU", "1")
+        else:
+            monkeypatch.delenv("HODE_READOUT_VALU", raising=False)
+        for D in (4, 6, 8, 12):
+            for obs in range(4, 129, 4):
+                for rows in (1, 37, 1000, 40000):
+                    d = L.ReadoutDesc()
+                    d.struct_size = ctypes.sizeof(L.ReadoutDesc)
+                    d.latent_dim, d.obs_dim, d.rows = D, obs, rows
+                    want = kv.readout_waves(rows, obs, D, valu) * (1 + obs * D + obs) * 4
+                    assert lib.hode_readout_workspace_bytes(d) == want, (valu, D, obs, rows)
+    assert [o for o in range(4, 129, 4) if kv.readout_mf(12, o)] == [52, 56, 60, 64, 68, 72, 76, 80]
+    assert [o for o in range(4, 129, 4) if kv.readout_mf(8, o)] == [36, 40, 44, 48]
+    rc = [(c["D"], c["obs"]) for c in kv.CASES if c["family"] == "readout" and not c["valu"]]
+    for edge in ((12, 48), (12, 52), (12, 80), (12, 84), (8, 32), (8, 36), (8, 48), (8, 52)):
+        assert edge in rc, edge
+    assert "if (d->latent_dim == 20) HODE_RM(20) else HODE_RM(4)" in open(os.path.join(CSRC, "hode_readout_mlp.hip")).read()
+
+
+def test_neural_rule_matches_the_workspace_size(monkeypatch):
+    """hode_workspace_bytes(..., WS_RK_BWD) of the neural rhs: with grad_w1 (the on-chip backward) one block of
+    2 HT 256 + 16 floats of partials per 16-patient wave (HT = ceil(10 D / 16)), independent of T and the method; without
+    grad_w1, or with the lane layout, the four tapes (T - 1) stages (10 D + 10 D + D + 1 + D) B floats."""
+    import hode
+    from hode import _lib as L
+    lib = hode.lib()
+    buf = (ctypes.c_float * 4)()
+    al = lambda x: (x + 255) // 256 * 256  # noqa: E731
+
+    def size(D, B, T, method, onchip):
+        d = L.new_solve_desc()
+        d.rhs_kind, d.method, d.batch, d.latent_dim, d.n_times, d.hidden_dim = L.RHS_NEURAL, L.METHODS[method], B, D, T, 10 * D
+        if onchip:
+            d.grad_w1 = ctypes.addressof(buf)  # never dereferenced: only selects the on-chip layout
+        return lib.hode_workspace_bytes(d, L.WS_RK_BWD)
+
+    for env in (None, "t"):
+        if env:
+            monkeypatch.setenv("HODE_NEURAL_LAYOUT", env)
+        else:
+            monkeypatch.delenv("HODE_NEURAL_LAYOUT", raising=False)
+        for D in (4, 6, 8, 10, 12, 14):
+            HD, HT = 10 * D, (10 * D + 15) // 16
+            for B in (1, 16, 17, 64, 65, 129):
+                for T in (1, 2, 6):
+                    for method, ns in (("euler", 1), ("midpoint", 2), ("rk4", 4)):
+                        w2t = al(HD * D * 4)
+                        inst = (T - 1) * ns
+                        tapes = w2t + al(inst * HD * B * 4) * 2 + al(inst * (D + 1) * B * 4) + al(inst * D * B * 4)
+                        onchip = w2t + al(kv.neural_grid(B, "mf") * (2 * HT * 256 + 16) * 4)
+                        for oc in (True, False):
+                            want = onchip if oc and not env else tapes
+                            assert size(D, B, T, method, oc) == want, (env, D, B, T, method, oc)
