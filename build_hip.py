@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Build libhode.so (gfx950) in-tree with hipcc: `python build_hip.py [-j N] [--force]`."""
+"""Build libhode.so and libhode_flow.so (gfx950) in-tree with hipcc: `python build_hip.py [-j N] [--force]`."""
 import argparse
 import concurrent.futures as cf
 import hashlib
@@ -12,6 +12,11 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(ROOT, "hybrid-ode-neurips-2021_amd", "csrc")
 OUT = os.path.join(ROOT, "hybrid-ode-neurips-2021_amd", "hode", "libhode.so")
 OBJ = os.path.join(CSRC, "build")
+# the planar-flow posterior is a library of its own (C ABI include/hode_flow.h): its kernels stay out of libhode.so
+FLOW_CSRC = os.path.join(CSRC, "flow")
+FLOW_OBJ = os.path.join(FLOW_CSRC, "build")
+FLOW_OUT = os.path.join(os.path.dirname(OUT), "libhode_flow.so")
+FLOW_HEADER = os.path.join(ROOT, "include", "hode_flow.h")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-variable",
          "-Wno-unused-but-set-variable"]
@@ -62,6 +67,23 @@ def source_digest():
     return h.hexdigest()
 
 
+def flow_units():
+    return [("hode_flow", os.path.join(FLOW_CSRC, "hode_flow.hip"), [])]
+
+
+def flow_source_digest():
+    """sha256 over everything libhode_flow.so is built from (its sources, its ABI header, the shared device helpers, the
+    flags); written next to the library, compared by tests/test_flow_host.py."""
+    h = hashlib.sha256()
+    files = [FLOW_HEADER, os.path.join(CSRC, "hode_common.hpp")] + sorted(
+        os.path.join(FLOW_CSRC, f) for f in os.listdir(FLOW_CSRC) if f.endswith((".hpp", ".hip", ".h")))
+    for f in files:
+        h.update(os.path.basename(f).encode())
+        h.update(open(f, "rb").read())
+    h.update(repr((FLAGS, flow_units())).encode().replace(ROOT.encode(), b""))
+    return h.hexdigest()
+
+
 def _deps_newest(obj, src):
     """Newest mtime among the files `obj` was compiled from (the -MD depfile hipcc left next to it), the ABI header and this
     script; None if there is no usable depfile (then the unit is rebuilt)."""
@@ -82,8 +104,8 @@ def _deps_newest(obj, src):
     return max(ts)
 
 
-def compile_one(name, src, extra, force, dep_time):
-    obj = os.path.join(OBJ, name + ".o")
+def compile_one(name, src, extra, force, dep_time, obj_dir=OBJ):
+    obj = os.path.join(obj_dir, name + ".o")
     flags_txt = " ".join(FLAGS + extra)
     stamp = obj[:-2] + ".flags"
     if not force and os.path.exists(obj):
@@ -126,7 +148,31 @@ def build(jobs=7, force=False, verbose=True):
             print("  linked", os.path.relpath(OUT, ROOT), flush=True)
     with open(OUT + ".digest", "w") as f:
         f.write(source_digest() + "\n")
+    build_flow(jobs, force, verbose)
     return OUT
+
+
+def build_flow(jobs=1, force=False, verbose=True):
+    """libhode_flow.so from csrc/flow/ (objects in csrc/flow/build/)."""
+    os.makedirs(FLOW_OBJ, exist_ok=True)
+    us = flow_units()
+    for n, s, e in us:
+        name, dt, err = compile_one(n, s, e, force, 0.0, FLOW_OBJ)
+        if verbose and dt:
+            print("  hipcc %-14s %.1fs" % (name, dt), flush=True)
+        if verbose and err.strip():
+            print(err[-2000:], file=sys.stderr)
+    objs = [os.path.join(FLOW_OBJ, n + ".o") for n, _, _ in us]
+    if force or not os.path.exists(FLOW_OUT) or os.path.getmtime(FLOW_OUT) < max(os.path.getmtime(o) for o in objs):
+        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", FLOW_OUT] + objs
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("link failed:\n" + r.stderr[-4000:])
+        if verbose:
+            print("  linked", os.path.relpath(FLOW_OUT, ROOT), flush=True)
+    with open(FLOW_OUT + ".digest", "w") as f:
+        f.write(flow_source_digest() + "\n")
+    return FLOW_OUT
 
 
 def build_variant(tag, unit_flags, verbose=True):

@@ -14,8 +14,9 @@ latent ODE is integrated by the gfx950 kernels of ``libhode.so`` (``hode.odeint`
     EncoderLSTMReal / RocheODEReal / DecoderReal / VariationalInferenceReal  model.py:180-242, 570-657, 772-862, 1217-1261
     GRUODECell / DecoderRealBenchmark ("tlstm", "gruode" baselines)         model.py:865-966  (hode.seqdec kernels)
     NeuralODEReal / NeuralODEReal2nd ("neural", "2nd" baselines)           model.py:660-769  (hode.neural_real kernels)
+    EncoderPlanarLSTM / VariationalInferenceFlow (planar-flow posterior)   model.py:48-153, 1299-1380 (hode.flow kernels)
 
-Out of scope: flow encoders.
+Out of scope: Sylvester flows (unused by the reference).
 """
 
 from __future__ import annotations
@@ -26,6 +27,7 @@ import os
 import torch
 import torch.nn as nn
 
+import flow as flows
 import hode
 import sim_config
 from global_config import DTYPE, get_device
@@ -129,6 +131,87 @@ class EncoderLSTM(nn.Module, GaussianReparam):
             mu = torch.exp(mu) / 10
             log_var = log_var - 5.0
         return mu, log_var
+
+
+class EncoderPlanarLSTM(nn.Module):
+    """EncoderLSTM's window encoder with amortized planar-flow parameters (reference model.py:48-153): forward returns
+    (mu, log_var, u (B, K, D, 1), w (B, K, 1, D), b (B, K, 1, 1)); reparameterize draws z0 ~ N(mu, exp(log_var)), runs the
+    K planar flows and the exp(z - 5) output layer.
+
+    HIP tensors: the window goes through the LSTM kernels (``hode.lstm``) and the five heads are one product over the
+    concatenated weights.  ``reparameterize`` is the reference's per-draw call surface in eager arithmetic; the training
+    and evaluation paths (``VariationalInferenceFlow.loss``, ``training_utils.evaluate_flow``) draw all samples at once
+    through the fused kernel pair of ``hode.flow``."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim, num_flows, normalize=True, device=None):
+        super().__init__()
+        self.device = get_device() if device is None else device
+        self.hidden_dim = hidden_dim
+        self.normalize = normalize
+        self.model_name = "PlanarLSTMEncoder"
+        # creation order lstm -> lin -> log_var -> amor_u -> amor_w -> amor_b -> flow_k: seeded init and state_dict keys
+        self.lstm = nn.LSTM(input_dim, hidden_dim).to(self.device)
+        self.lin = nn.Linear(hidden_dim, output_dim).to(self.device)
+        self.log_var = nn.Linear(hidden_dim, output_dim).to(self.device)
+        self.q_z_nn_output_dim = hidden_dim
+        self.num_flows = num_flows
+        self.z_size = output_dim
+        self.log_det_j = 0.0
+        self.amor_u = nn.Linear(self.q_z_nn_output_dim, self.num_flows * self.z_size).to(self.device)
+        self.amor_w = nn.Linear(self.q_z_nn_output_dim, self.num_flows * self.z_size).to(self.device)
+        self.amor_b = nn.Linear(self.q_z_nn_output_dim, self.num_flows).to(self.device)
+        for k in range(self.num_flows):
+            self.add_module("flow_" + str(k), flows.Planar().to(self.device))
+
+    final_hidden = EncoderLSTM.final_hidden
+
+    def _heads(self):
+        return (self.lin, self.log_var, self.amor_u, self.amor_w, self.amor_b)
+
+    def forward(self, x, a, mask):
+        h = self.final_hidden(x, a, mask)
+        B, D, K = h.shape[0], self.z_size, self.num_flows
+        if h.is_cuda:   # one product over the concatenated heads; gradients reach every head through the cat
+            heads = self._heads()
+            out = _TallLinear.apply(h, torch.cat([m.weight for m in heads]), torch.cat([m.bias for m in heads]))
+            mu, log_var, u, w, b = torch.split(out, [D, D, K * D, K * D, K], dim=1)
+        else:
+            mu, log_var, u, w, b = (m(h) for m in self._heads())
+        u = u.reshape(B, K, D, 1)
+        w = w.reshape(B, K, 1, D)
+        b = b.reshape(B, K, 1, 1)
+        if self.normalize:
+            mu = torch.exp(mu) / 10
+            log_var = log_var - 5.0
+        return mu, log_var, u, w, b
+
+    def reparameterize(self, mu, log_var, u, w, b):
+        log_det_j = 0.0
+        z = [GaussianReparam.reparameterize(mu, log_var)]
+        for k in range(self.num_flows):
+            z_k, log_det_jacobian = getattr(self, "flow_" + str(k))(z[k], u[:, k, :, :], w[:, k, :, :], b[:, k, :, :])
+            z.append(z_k)
+            log_det_j += log_det_jacobian
+        z_exp = torch.exp(z_k - 5.0)
+        log_det_j += torch.sum(z_k - 5.0, dim=-1)
+        return mu, log_var, z_exp, log_det_j, z[0]
+
+    def log_density(self, mu, log_var, z_1, log_det_j, z0):
+        return GaussianReparam.log_density(mu, log_var, z0) - log_det_j
+
+    def flow_draws(self, mu, log_var, u, w, b, eps):
+        """Eager (CPU) restatement of S reparameterize calls with given draws eps (S, B, D): returns z_out (S, B, D),
+        log_det_j (S, B), z0 (S, B, D) -- the reference's per-draw arithmetic on S * B rows."""
+        S, B, D = eps.shape
+        z0 = eps * torch.exp(0.5 * log_var) + mu
+        z = z0.reshape(S * B, D)
+        rep = lambda t: t.unsqueeze(0).expand((S,) + tuple(t.shape)).reshape((S * B,) + tuple(t.shape[1:]))
+        log_det_j = 0.0
+        for k in range(self.num_flows):
+            z, ld = getattr(self, "flow_" + str(k))(z, rep(u[:, k]), rep(w[:, k]), rep(b[:, k]))
+            log_det_j = log_det_j + ld
+        log_det_j = log_det_j + torch.sum(z - 5.0, dim=-1)
+        return torch.exp(z - 5.0).reshape(S, B, D), log_det_j.reshape(S, B), z0
 
 
 dose_schedule_index = hode.solver.dose_schedule_index
@@ -894,3 +977,77 @@ class VariationalInferenceReal(VariationalInference):
         else:
             kld = torch.mean(self.mc_kl(mu, log_var, self.mc_size), dim=0)
         return lik + kld
+
+
+class VariationalInferenceFlow:
+    """Negative ELBO with the planar-flow posterior (reference model.py:1299-1380): masked SSE of one flow draw's
+    decode + Monte-Carlo KL of ``mc_size`` further draws against the prior.  With ``mc_size == 1`` the decoder's draw
+    is reused and the KL term is ``mean(log_p - log_q)`` -- the reference's sign, kept as is.
+
+    HIP tensors: all 1 + mc_size draws come from one (S, B, D) ``randn`` block and go through one fused forward and one
+    fused backward launch (``hode.flow.planar_flow_sample``); the likelihood takes the fused readout + masked-SSE path.
+    RNG stream: the reference draws (B, D) per ``reparameterize`` call (decoder draw first, then the KL draws); here the
+    same draws come from one (1 + mc_size, B, D) tensor in the same order, so the numbers differ from a seeded reference
+    run although the distribution is the same.  The prior must be ``ExponentialPrior.log_density`` on the device (the
+    kernel's prior); ``prior_log_pdf=None`` fails as in the reference (TypeError)."""
+
+    def __init__(self, encoder, decoder, elbo=True, prior_log_pdf=None, mc_size=100):
+        self.encoder = encoder
+        self.decoder = decoder
+        self.prior_log_pdf = prior_log_pdf
+        self.mc_size = mc_size
+        self.elbo = elbo
+        self.fuse_likelihood = True
+        self.model_name = "VI_FLOW_{}_{}.pkl".format(encoder.model_name, decoder.model_name)
+
+    def save(self, path, itr, best_loss):
+        path = path + self.model_name
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        torch.save({"itr": itr, "encoder_state_dict": self.encoder.state_dict(),
+                    "decoder_state_dict": self.decoder.state_dict(), "best_loss": best_loss}, path)
+
+    def parameters(self):
+        return list(self.encoder.parameters()) + list(self.decoder.parameters())
+
+    def noise(self, n_samples, like):
+        """The standard-normal draws of one loss call: (n_samples, B, D), sample axis first."""
+        return torch.randn((n_samples,) + tuple(like.shape), device=like.device, dtype=like.dtype)
+
+    def flow_kl(self, encoder_out, eps, s_kl):
+        """(z_out (S, B, D), kl (B,)): the flow draws of eps and the mean over draws s_kl.. of log q - log p."""
+        mu, log_var, u, w, b = encoder_out
+        if self.prior_log_pdf is None:
+            raise TypeError("'NoneType' object is not callable")  # the reference calls prior_log_pdf(z)
+        if mu.is_cuda:
+            if self.prior_log_pdf is not ExponentialPrior.log_density:
+                raise hode.HodeConfigError("VariationalInferenceFlow: the device path implements the Exponential(100) "
+                                           "prior only (ExponentialPrior.log_density)")
+            from hode.flow import planar_flow_sample
+            return planar_flow_sample(mu, log_var, u, w, b, eps, s_kl)
+        z_out, log_det_j, z0 = self.encoder.flow_draws(mu, log_var, u, w, b, eps)
+        log_q = self.encoder.log_density(mu, log_var, z_out, log_det_j, z0)
+        return z_out, torch.mean((log_q - self.prior_log_pdf(z_out))[s_kl:], dim=0)
+
+    def loss(self, data):
+        x, a, mask = data["measurements"], data["actions"], data["masks"]
+        self.x, self.a, self.mask = x, a, mask
+        encoder_out = self.encoder(x, a, mask)
+        mu = encoder_out[0]
+        single = self.mc_size == 1
+        eps = self.noise(1 if single else 1 + self.mc_size, mu)
+        z_all, kl = self.flow_kl(encoder_out, eps, 0 if single else 1)
+        z = z_all[0]
+        self.z = z
+        fused = getattr(self.decoder, "fused_likelihood_ok", None)
+        if self.fuse_likelihood and fused is not None and fused(x):
+            h_hat = self.decoder.latent(z, a)
+            self.h_hat, self._x_hat = h_hat, None
+            lik = self.decoder.masked_sse(h_hat, x, mask)
+        else:
+            x_hat, h_hat = self.decoder(z, a)
+            self._x_hat, self.h_hat = x_hat, h_hat
+            lik = torch.sum((x - x_hat) ** 2 * mask) / x.shape[1]
+        kld = torch.mean(-kl if single else kl, dim=0)
+        return lik + kld if self.elbo else lik
+
+    x_hat = VariationalInference.x_hat

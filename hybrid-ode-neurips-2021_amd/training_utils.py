@@ -246,3 +246,51 @@ def evaluate_horizon(model, data_generator, batch_size, t0, mc_itr=10, real=Fals
     cprs_x, cprs_x_sd = _mean_with_standard_error(np.concatenate(crps_x_all, axis=1), axis=1)
     return {"rmse_x": np.array([r for r, _ in per_step], dtype=np.float32), "rmse_x_sd": np.array([sd for _, sd in per_step]),
             "cprs_x": cprs_x, "cprs_x_sd": cprs_x_sd}
+
+
+def evaluate_flow(model, data_generator, batch_size, t0, mc_itr=50, real=False):
+    """Reference ``training_utils.evaluate_flow`` (:282-378) for ``VariationalInferenceFlow``: per test chunk one flow
+    draw is the point estimate and ``mc_itr`` further draws form the ensemble; all 1 + mc_itr draws come from one fused
+    kernel call (``hode.flow``), the ensemble is decoded as one mc_itr * B batch and scored by the CRPS kernel, as
+    ``evaluate`` does.  Kept literally from the reference: ``z0`` there is rebound by every ``reparameterize`` call, so
+    ``rmse_z0`` compares the point draw with its own base sample z0 = eps * sigma + mu, and ``cprs_z0`` scores the
+    ensemble against the LAST draw's base sample.  Prints the four ``name,value,sd`` lines; ``real=True`` raises
+    ValueError as the reference does."""
+    from hode.flow import planar_flow_sample
+
+    per_chunk = {"se_z0": [], "mse_x": [], "crps_z0": [], "crps_x": []}
+    E = data_generator.expert_dim
+    M = int(mc_itr)
+    with torch.no_grad():
+        for chunk in range(data_generator.test_size // batch_size):
+            data = data_generator.get_split("test", batch_size, chunk)
+            x, a, mask = data["measurements"][:t0], data["actions"][:t0], data["masks"][:t0]
+            if real:
+                raise ValueError
+            mu, log_var, u, w, b = model.encoder(x, a, mask)
+            eps = model.noise(1 + M, mu)
+            z_all, _ = planar_flow_sample(mu, log_var, u, w, b, eps, s_kl=1)
+            base = eps[:: max(M, 1)] * torch.exp(0.5 * log_var) + mu     # base samples of draw 0 and draw M
+            z0_hat = z_all[0]
+            x_hat, _ = model.decoder(z0_hat, data["actions"])
+            x_hat = x_hat[t0:]
+            per_chunk["se_z0"].append(torch.sum((base[0][:, :E] - z0_hat[:, :E]) ** 2, dim=1).cpu())
+            x_test, mask_test = data["measurements"][t0:], data["masks"][t0:]
+            per_chunk["mse_x"].append((torch.sum((x_test - x_hat) ** 2 * mask_test, dim=(0, 2))
+                                       / torch.sum(mask_test, dim=(0, 2))).cpu())
+            B, D = mu.shape
+            z_flat = z_all[1:].reshape(M * B, D)
+            lin = model.decoder.output_function[0]
+            h_mc = model.decoder.latent(z_flat, data["actions"].repeat(1, M, 1))
+            crps_x = _ensemble_crps(h_mc[t0:], x_test, M, weight=lin.weight, bias=lin.bias) / x_test.shape[2]
+            crps_z0 = _ensemble_crps(z_flat.unsqueeze(0), base[-1][:, :E].unsqueeze(0).contiguous(), M)[0] / E
+            per_chunk["crps_z0"].append(crps_z0.cpu().numpy())
+            per_chunk["crps_x"].append(crps_x.mean(dim=0).cpu().numpy())
+    rmse_z0, rmse_z0_sd = _rmse_with_bootstrap(torch.cat(per_chunk["se_z0"]))
+    rmse_x, rmse_x_sd = _rmse_with_bootstrap(torch.cat(per_chunk["mse_x"]))
+    cprs_z0, cprs_z0_sd = _mean_with_standard_error(np.concatenate(per_chunk["crps_z0"]))
+    cprs_x, cprs_x_sd = _mean_with_standard_error(np.concatenate(per_chunk["crps_x"]))
+    for name, value, sd in (("rmse_z0", rmse_z0, rmse_z0_sd), ("rmse_x", rmse_x, rmse_x_sd),
+                            ("cprs_z0", cprs_z0, cprs_z0_sd), ("cprs_x", cprs_x, cprs_x_sd)):
+        print("{},{:.4f},{:.4f}".format(name, value, sd))
+    return rmse_z0, rmse_z0_sd, cprs_z0, rmse_x, rmse_x_sd, cprs_x
