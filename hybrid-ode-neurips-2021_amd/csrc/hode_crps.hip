@@ -35,7 +35,7 @@ __global__ __launch_bounds__(kCrpsThreads) void crps_kernel(CrpsArgs a) {
   float* hm = lds;                                        // [M][Dv] member vectors of this row
   float* wT = hm + a.M * a.Dv;                            // [Dv][128] readout, component-minor (conflict-free)
   float* vals = wT + (a.w ? a.Dv * kCrpsThreads : 0);     // [M][128] ensemble values, one column per thread
-  __shared__ float red[kCrpsThreads / 64];
+  float* red = vals + a.M * kCrpsThreads;                 // [2] per-wave partials of crps_sum
   const int tid = threadIdx.x;
   const long long row = blockIdx.x;
   const int t = (int)(row / a.B), b = (int)(row % a.B);
@@ -105,8 +105,9 @@ extern "C" int hode_ensemble_crps(const hode_crps_desc* d, void* stream) {
   a.h = d->h; a.w = d->w; a.b = d->b; a.truth = d->truth; a.crps = d->crps; a.crps_sum = d->crps_sum;
   a.ts = d->time_stride; a.ms = d->member_stride; a.ps = d->patient_stride;
   a.B = d->batch; a.M = d->n_members; a.Dv = d->latent_dim; a.obs = d->obs_dim;
+  // the whole LDS of the kernel (it declares no static __shared__): members, readout, values, the two wave partials
   const size_t lds = sizeof(float) * ((size_t)a.M * a.Dv + (a.w ? (size_t)a.Dv * hode::kCrpsThreads : 0) +
-                                      (size_t)a.M * hode::kCrpsThreads);
+                                      (size_t)a.M * hode::kCrpsThreads + hode::kCrpsThreads / 64);
   if (lds > 160 * 1024) return hode::fail(HODE_E_UNSUPPORTED, "needs %zu B of LDS", lds);
   if (lds > 64 * 1024)
     if (int e = hode::hip_fail(hipFuncSetAttribute((const void*)hode::crps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,

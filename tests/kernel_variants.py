@@ -702,8 +702,9 @@ UNREACHABLE_BODIES = {}
 # kernel symbols of the library outside FAMILIES -> the test that checks them against a float64 reference
 # (tests/test_kernel_variant_coverage.py: every `.kd` symbol of the build is in FAMILIES or here)
 OTHER_KERNELS = {
-    "hode::crps_kernel": "tests/test_hip_crps.py::test_linear_readout_crps_vs_oracle",
-    "hode::mc_kl_exp_kernel": "tests/test_hip_mckl.py::test_fused_mc_kl_matches_reference_loop",
+    # the metric kernels have a case table of their own (tests/metric_cases.py, guarded by tests/test_metric_case_coverage.py)
+    "hode::crps_kernel": "tests/test_hip_metric_cases.py::test_crps_case",
+    "hode::mc_kl_exp_kernel": "tests/test_hip_metric_cases.py::test_mckl_case",
     # the weight / theta gradient fold behind the Roche lane-kernel backward (csrc/hode_api.hip:255), the Roche dopri5
     # backward (csrc/hode_dopri5.hip:264, :274) and hode_real.hip (:412): every lane / dopri5 / real_kernel case runs it
     "hode::fold_partials_kernel": "tests/test_hip_kernel_variants.py::test_roche_fixed_grid",

@@ -101,3 +101,70 @@ def test_evaluate_on_gpu_matches_oracle_crps_on_the_same_draws(monkeypatch, caps
     np.testing.assert_allclose(np.array(got), np.array(ref), rtol=2e-5)
     hz = training_utils.evaluate_horizon(vi, dg, 6, t0, mc_itr=10)
     assert hz["cprs_x"].shape == (T - t0,) and np.all(np.isfinite(hz["cprs_x"]))
+
+
+def _oracle_on_gpu_tensors(h, truth, M, weight=None, bias=None, per_component=False):
+    from test_evaluate import oracle_ensemble_crps
+    c = oracle_ensemble_crps(h.cpu(), truth.cpu(), M, None if weight is None else weight.cpu(),
+                             None if bias is None else bias.cpu(), per_component)
+    return c.to(h.device)
+
+
+def test_evaluate_horizon_on_gpu_matches_oracle_crps_on_the_same_draws(monkeypatch):
+    """evaluate_horizon (mc_itr 10, real=False: the linear readout of the latent trajectory) with the CRPS kernel and
+    with the oracle swapped in, on identical draws: every per-step number agrees to fp32 noise."""
+    dev = _dev()
+    import model
+    import training_utils
+    from test_evaluate import FakeGenerator
+    obs, D, T, step, t0 = 20, 6, 15, 0.125, 5
+    dg = FakeGenerator(24, T, obs, D, seed=9, step=step)
+    dg.data = {k: v.to(dev) for k, v in dg.data.items()}
+    torch.manual_seed(23)
+    enc = model.EncoderLSTM(obs + 1, 2 * obs, D, device=dev)
+    dec = model.RocheExpertDecoder(obs, D, 1, (T - 1) * step, step, method="rk4", device=dev)
+    vi = model.VariationalInference(enc, dec, elbo=True)
+    out = []
+    for swap in (False, True):
+        if swap:
+            monkeypatch.setattr(training_utils, "_ensemble_crps", _oracle_on_gpu_tensors)
+        torch.manual_seed(8)
+        torch.cuda.manual_seed(8)
+        out.append(training_utils.evaluate_horizon(vi, dg, 12, t0, mc_itr=10))
+    got, ref = out
+    assert got["cprs_x"].shape == (T - t0,) and np.all(ref["cprs_x"] > 0)
+    for k in ("cprs_x", "cprs_x_sd", "rmse_x"):
+        np.testing.assert_allclose(got[k], ref[k], rtol=2e-5, err_msg=k)
+
+
+def test_evaluate_real_on_gpu_matches_oracle_crps_on_the_same_draws(monkeypatch, capsys):
+    """evaluate(real=True) on a reduced config-5 mirror (obs 24, statics 11, D 20, hybrid rhs, midpoint): the decoder's
+    own output is scored through the identity readout (latent_dim = obs_dim = 24).  Kernel vs oracle on the same draws."""
+    dev = _dev()
+    import model
+    import training_utils
+    from hode.batches import DeviceFolds
+    obs, act, stat, D, T, t0, N = 24, 1, 11, 20, 30, 12, 60
+    input_dim = obs + act + stat + 1
+    hidden = int((obs + act + stat) * 1.2)
+    gen = torch.Generator().manual_seed(6)
+    folds = DeviceFolds(torch.randn(T, N, obs, generator=gen),
+                        (torch.rand(T, N, 1, generator=gen) < 0.15).float() * torch.rand(T, N, 1, generator=gen),
+                        torch.rand(T, N, 4, generator=gen) * 0.05, (torch.rand(T, N, obs, generator=gen) < 0.5).float(),
+                        10, 40, statics=torch.rand(1, N, stat, generator=gen).expand(T, N, stat), device=dev)
+    torch.manual_seed(2)
+    enc = model.EncoderLSTMReal(input_dim, int(input_dim * 1.2), D, output_all=False, reverse=False)
+    dec = model.DecoderReal(obs, D, act, stat, hidden, T, 1, t0=0, method="midpoint", ode_step_size=1.0,
+                            ode_type="hybrid")
+    vi = model.VariationalInferenceReal(enc, dec, elbo=False, t0=t0)
+    out = []
+    for swap in (False, True):
+        if swap:
+            monkeypatch.setattr(training_utils, "_ensemble_crps", _oracle_on_gpu_tensors)
+        torch.manual_seed(4)
+        torch.cuda.manual_seed(4)
+        out.append(training_utils.evaluate(vi, folds, 20, t0, mc_itr=10, real=True))
+    capsys.readouterr()
+    got, ref = np.array(out[0]), np.array(out[1])
+    assert np.all(np.isfinite(ref)) and ref[5] > 0 and ref[2] > 0
+    np.testing.assert_allclose(got, ref, rtol=2e-5)

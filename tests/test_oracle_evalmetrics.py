@@ -2,7 +2,7 @@
 the anchors its docstring lists."""
 import numpy as np
 
-from oracle.evalmetrics import crps_ensemble, crps_ensemble_cdf, crps_field
+from oracle.evalmetrics import crps_ensemble, crps_ensemble_cdf, crps_field, crps_sorted
 
 
 def test_single_member_is_absolute_error():
@@ -45,3 +45,26 @@ def test_field_matches_scalar_loop():
             for k in range(5):
                 ref[i, j, k] = crps_ensemble(truth[i, j, k], ens[i, j, k])
     assert np.abs(crps_field(truth, ens) - ref).max() < 1e-13
+
+
+def test_sorted_form_matches_the_pairwise_and_cdf_forms():
+    """crps_sorted (the O(M log M) oracle of the CRPS kernel tests) against crps_ensemble, crps_ensemble_cdf and
+    crps_field, with ties, a truth on a member, one member, and a large common offset."""
+    rng = np.random.default_rng(6)
+    for m in (1, 2, 3, 7, 50, 128):
+        for _ in range(10):
+            x = rng.normal(size=m) * rng.uniform(0.1, 3.0)
+            y = rng.normal() * 2.0
+            ref = crps_ensemble(y, x)
+            assert abs(float(crps_sorted(y, x)) - ref) < 1e-12
+            assert abs(float(crps_sorted(y, x)) - crps_ensemble_cdf(y, x)) < 1e-12
+    x = np.array([0.5, -1.0, 0.5, 2.0, -1.0, 0.5])                      # ties
+    assert abs(float(crps_sorted(0.5, x)) - crps_ensemble(0.5, x)) < 1e-15
+    assert float(crps_sorted(0.5, np.full(9, 0.5))) == 0.0            # zero spread on the truth
+    assert float(crps_sorted(1.5, np.full(4, -0.25))) == 1.75         # all members equal: |x - y|
+    assert float(crps_sorted(1.5, [0.25])) == 1.25
+    x = 1000.0 + rng.normal(size=40) * 1e-2                           # offset 1e3, spread 1e-2
+    assert abs(float(crps_sorted(1000.0, x)) - crps_ensemble(1000.0, x)) < 1e-12
+    truth = rng.normal(size=(3, 4, 5))
+    ens = rng.normal(size=(3, 4, 5, 11))
+    assert np.abs(crps_sorted(truth, ens) - crps_field(truth, ens)).max() < 1e-13
