@@ -52,6 +52,8 @@ def _status_error(status):
 
 
 class _RocheDopri5(torch.autograd.Function):
+    """Gradients for y0, theta, w, b; none for t, dosage, dose_times (their .grad stays None)."""
+
     @staticmethod
     def forward(ctx, y0, theta, w, b, t, dosage, dose_times, rtol, atol, ablate, lanes, max_steps, detach_first_step,
                 grad_enabled=True):
@@ -118,7 +120,7 @@ class _RocheDopri5(torch.autograd.Function):
         rtol, atol, ablate, lanes, has_w, steps, n_accepted, detach_first = ctx.meta
         lib = L.lib()
         T, B, D = h.shape
-        gh = grad_h.to(torch.float32).contiguous()
+        gh = _f32c(grad_h)
         need_th = bool(ctx.needs_input_grad[1])
         gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)
         gth = torch.zeros(L.N_THETA, device=h.device, dtype=torch.float32)
@@ -158,7 +160,8 @@ def roche_dopri5(y0, theta, w, b, t, dosage, dose_times, rtol=1e-7, atol=1e-9, a
 
 class _NeuralDopri5(torch.autograd.Function):
     """NeuralODE rhs (reference model.py:969-1026) through ``hode_dopri5_fwd / _bwd`` with ``HODE_RHS_NEURAL``: the MFMA
-    attempt kernels of csrc/hode_neural_dopri5.hip; the backward accumulates the weight gradients on chip."""
+    attempt kernels of csrc/hode_neural_dopri5.hip; the backward accumulates the weight gradients on chip.  Gradients for y0
+    and the four weights; none for t, dosage, dose_times (their .grad stays None)."""
 
     @staticmethod
     def forward(ctx, y0, w1, b1, w2, b2, t, dosage, dose_times, rtol, atol, max_steps, detach_first_step, grad_enabled=True):
@@ -215,7 +218,7 @@ class _NeuralDopri5(torch.autograd.Function):
         rtol, atol, steps, n_accepted, detach_first = ctx.meta
         lib = L.lib()
         T, B, D = h.shape
-        gh = grad_h.to(torch.float32).contiguous()
+        gh = _f32c(grad_h)
         gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)
         gw1, gb1, gw2, gb2 = (torch.zeros_like(x) for x in (w1c, b1c, w2c, b2c))
         n_acc = C.c_int32(n_accepted)

@@ -35,6 +35,8 @@ def _desc(mu, lv, u, w, b, noise, s_kl):
 
 
 class _PlanarFlowKL(torch.autograd.Function):
+    """Gradients for mu, log_var, u, w, b; none for noise (its .grad stays None)."""
+
     @staticmethod
     def forward(ctx, mu, log_var, u, w, b, noise, s_kl, want_z):
         _require_gpu(mu, log_var, u, w, b, noise)

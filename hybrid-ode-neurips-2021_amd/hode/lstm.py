@@ -117,7 +117,8 @@ def _side_stream(device):
 
 
 class _LstmEncode(torch.autograd.Function):
-    """h_final = LSTM(window); backward = BPTT kernel + one split-K BLAS GEMM over K = T*B for all weight and bias gradients."""
+    """h_final = LSTM(window); backward = BPTT kernel + one split-K BLAS GEMM over K = T*B for all weight and bias gradients.
+    Gradients for the four LSTM parameters; none for x, a, mask (their .grad stays None)."""
 
     @staticmethod
     def forward(ctx, x, a, mask, w_ih, w_hh, b_ih, b_hh, reverse):
@@ -150,7 +151,7 @@ class _LstmEncode(torch.autograd.Function):
         lib = L.lib()
         T, B, obs = xc.shape
         H = wh.shape[1]
-        gh = grad_h.to(torch.float32).contiguous()
+        gh = _f32c(grad_h)
         dgates = torch.empty((T, B, 4 * H), device=xc.device, dtype=torch.float32)
         ad = 0 if ac is None else ac.shape[-1]
         I = obs + ad

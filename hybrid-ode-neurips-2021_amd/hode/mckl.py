@@ -32,6 +32,8 @@ def _launch(mu, log_var, noise, rate, clamp_value, need):
 
 
 class _McKlExp(torch.autograd.Function):
+    """Gradients for mu and log_var; none for noise (its .grad stays None)."""
+
     @staticmethod
     def forward(ctx, mu, log_var, noise, rate, clamp_value):
         kl, gmu, glv = _launch(mu, log_var, noise, rate, clamp_value, True)

@@ -30,6 +30,8 @@ def _desc(y0, t, dosage, dose_times, w1, b1, w2, b2, h, method, perturb):
 
 
 class _NeuralFixedGrid(torch.autograd.Function):
+    """Gradients for y0 and the four weights; none for t, dosage, dose_times (their .grad stays None)."""
+
     @staticmethod
     def forward(ctx, y0, w1, b1, w2, b2, t, dosage, dose_times, method, perturb):
         _require_gpu(y0, w1, t, dosage, dose_times)
@@ -54,7 +56,7 @@ class _NeuralFixedGrid(torch.autograd.Function):
         method, perturb = ctx.meta
         lib = L.lib()
         T, B, D = h.shape
-        gh = grad_h.to(torch.float32).contiguous()
+        gh = _f32c(grad_h)
         gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)
         d = _desc(h[0], tc, dosc, dtc, w1c, b1c, w2c, b2c, h, method, perturb)
         d.grad_h, d.grad_y0 = gh.data_ptr(), gy0.data_ptr()

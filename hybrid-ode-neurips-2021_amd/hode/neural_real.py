@@ -94,6 +94,9 @@ def _desc(kind, y0, t, dose, w1, b1, w2, b2, h, method):
 
 
 class _NeuralRealFixedGrid(torch.autograd.Function):
+    """Gradients for y0 and the four weights; none for t and the dose table gathered from the action a (their .grad
+    stays None)."""
+
     @staticmethod
     def forward(ctx, y0, w1, b1, w2, b2, t, dose, kind, method):
         lib = L.lib()
@@ -114,7 +117,7 @@ class _NeuralRealFixedGrid(torch.autograd.Function):
         kind, method = ctx.meta
         lib = L.lib()
         T, B, D = h.shape
-        gh = grad_h.to(torch.float32).contiguous()
+        gh = _f32c(grad_h)
         gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)
         gw1, gb1, gw2, gb2 = (torch.zeros_like(x) for x in (w1c, b1c, w2c, b2c))
         d = _desc(kind, h[0], tc, dc, w1c, b1c, w2c, b2c, h, method)

@@ -10,6 +10,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
+from .solver import _f32c
 
 
 class RocheRKPlan:
@@ -24,13 +25,13 @@ class RocheRKPlan:
         T = t.numel()
         self.B, self.D, self.T = B, D, T
         f32 = dict(device=self.dev, dtype=torch.float32)
-        self.y0 = y0.detach().to(torch.float32).contiguous()
-        self.theta = theta.detach().to(torch.float32).contiguous()
-        self.w = None if w is None else w.detach().to(torch.float32).contiguous()
-        self.b = None if b is None else b.detach().to(torch.float32).contiguous()
-        self.t = t.detach().to(torch.float32).contiguous()
-        self.dosage = dosage.detach().to(torch.float32).contiguous()
-        self.dose_times = dose_times.detach().to(torch.float32).reshape(B, -1).contiguous()
+        self.y0 = _f32c(y0)
+        self.theta = _f32c(theta)
+        self.w = None if w is None else _f32c(w)
+        self.b = None if b is None else _f32c(b)
+        self.t = _f32c(t)
+        self.dosage = _f32c(dosage)
+        self.dose_times = _f32c(dose_times.reshape(B, -1))
         self.h = torch.empty((T, B, D), **f32)
         self.grad_h = torch.zeros((T, B, D), **f32)
         self.grad_y0 = torch.empty((B, D), **f32)

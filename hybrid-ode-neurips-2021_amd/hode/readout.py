@@ -16,6 +16,8 @@ def supported(latent_dim: int, obs_dim: int) -> bool:
 
 
 class _ReadoutSSE(torch.autograd.Function):
+    """Gradients for h, w, b; none for x and mask (their .grad stays None)."""
+
     @staticmethod
     def forward(ctx, h, x, mask, w, b):
         _require_gpu(h, x, mask, w, b)
@@ -62,6 +64,8 @@ def mlp_supported(latent_dim: int, hidden_dim: int, obs_dim: int) -> bool:
 
 
 class _ReadoutMlpSSE(torch.autograd.Function):
+    """Gradients for h and the four weights; none for x, mask, time_weight (their .grad stays None)."""
+
     @staticmethod
     def forward(ctx, h, x, mask, w1, b1, w2, b2, time_weight, skip):
         _require_gpu(h, x, mask, w1, w2)
@@ -86,9 +90,10 @@ class _ReadoutMlpSSE(torch.autograd.Function):
             if skip:
                 gh[:skip].zero_()
             # the four parameter-gradient accumulators as views of ONE zeroed buffer: one fill here, one scaling in backward
-            sizes = [t.numel() for t in (w1c, b1c, w2c, b2c)]
+            # (each padded to a multiple of 4 floats, so that every one starts on a 16-byte boundary)
+            sizes = [(t.numel() + 3) // 4 * 4 for t in (w1c, b1c, w2c, b2c)]
             gflat = torch.zeros(sum(sizes), device=h.device, dtype=torch.float32)
-            gw1, gb1, gw2, gb2 = (v.view(t.shape) for v, t in zip(torch.split(gflat, sizes), (w1c, b1c, w2c, b2c)))
+            gw1, gb1, gw2, gb2 = (v[:t.numel()].view(t.shape) for v, t in zip(torch.split(gflat, sizes), (w1c, b1c, w2c, b2c)))
             d.grad_h, d.grad_w1, d.grad_b1, d.grad_w2, d.grad_b2 = (gh.data_ptr() + off, gw1.data_ptr(), gb1.data_ptr(), gw2.data_ptr(),
                                                                     gb2.data_ptr())
         n = lib.hode_readout_mlp_workspace_bytes(d)
@@ -105,7 +110,7 @@ class _ReadoutMlpSSE(torch.autograd.Function):
     def backward(ctx, g):
         gh, gflat = ctx.saved_tensors
         sizes, shapes = ctx.shapes
-        gw1, gb1, gw2, gb2 = (v.view(sh) for v, sh in zip(torch.split(gflat * g, sizes), shapes))
+        gw1, gb1, gw2, gb2 = (v[:sh.numel()].view(sh) for v, sh in zip(torch.split(gflat * g, sizes), shapes))
         return gh * g, None, None, gw1, gb1, gw2, gb2, None, None
 
 

@@ -26,6 +26,8 @@ def _desc(y0, t, act, theta, wflat, h, method, perturb, hidden):
 
 
 class _RealFixedGrid(torch.autograd.Function):
+    """Gradients for y0, theta, wflat; none for t and the action table act (their .grad stays None)."""
+
     @staticmethod
     def forward(ctx, y0, theta, wflat, t, act, method, perturb, hidden):
         _require_gpu(y0, theta, wflat, t, act)
@@ -51,7 +53,7 @@ class _RealFixedGrid(torch.autograd.Function):
         method, perturb, H = ctx.meta
         lib = L.lib()
         T, B, D = h.shape
-        gh = grad_h.to(torch.float32).contiguous()
+        gh = _f32c(grad_h)
         gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)
         gth = torch.zeros(L.N_THETA, device=h.device, dtype=torch.float32)
         d = _desc(h[0], tc, ac, thc, wc, h, method, perturb, H)

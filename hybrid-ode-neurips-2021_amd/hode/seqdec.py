@@ -4,14 +4,15 @@ then one ``nn.LSTM`` call or a handful of small eager ops per step).
 
 ``tlstm``: LSTM(2, D) with h0 = c0 = init; the forward tapes the cell state, the BPTT kernel recomputes the gates from it.
 ``gruode``: ``GRUODECell`` as the reference calls it -- the hidden state handed to the cell stays ``init`` at every step,
-so every row is independent (no recurrence).  Both return gradients for ``init`` and every parameter; ``a`` takes none."""
+so every row is independent (no recurrence).  Both return gradients for ``init`` and every parameter; ``a``, ``idx`` and
+``tau`` take none (their ``.grad`` stays None).  ``idx`` may be any integer tensor and ``tau`` any float tensor."""
 
 from __future__ import annotations
 
 import torch
 
 from . import _lib as L
-from .solver import _f32c, _require_gpu, _stream
+from .solver import _f32c, _i32c, _require_gpu, _stream
 
 
 def step_tables(t, t_max, device):
@@ -49,6 +50,7 @@ def _desc(kind, init, a, idx, tau, w0, w1, b0, b1, h):
 def _forward(ctx, kind, init, a, idx, tau, w0, w1, b0, b1, tape):
     lib = L.lib()
     initc, ac = _f32c(init), _f32c(a)
+    idx, tau = _i32c(idx, "step index table"), _f32c(tau)   # the kernels read int32 rows and fp32 times, whatever came in
     w0c, w1c = _f32c(w0), _f32c(w1)
     b0c = None if b0 is None else _f32c(b0)
     b1c = None if b1 is None else _f32c(b1)
@@ -69,7 +71,7 @@ def _forward(ctx, kind, init, a, idx, tau, w0, w1, b0, b1, tape):
 def _backward(ctx, grad_h):
     initc, ac, idx, tau, w0c, w1c, b0c, b1c, h, c = ctx.saved_tensors
     lib = L.lib()
-    gh = grad_h.to(torch.float32).contiguous()
+    gh = _f32c(grad_h)
     d = _desc(ctx.kind, initc, ac, idx, tau, w0c, w1c, b0c, b1c, h)
     d.c = 0 if c is None else c.data_ptr()
     ginit, gw0, gw1 = torch.empty_like(initc), torch.empty_like(w0c), torch.empty_like(w1c)

@@ -22,8 +22,23 @@ def _require_gpu(*tensors):
             )
 
 
+def _aligned(x):
+    # a contiguous view into a larger buffer (a slice, one half of a torch.stack cotangent) keeps its storage offset:
+    # the kernels' 16-byte loads need their own copy of it
+    return x.clone() if x.data_ptr() % 16 else x
+
+
 def _f32c(x):
-    return x.detach().to(torch.float32).contiguous()
+    """What every tensor -- input or cotangent -- becomes before its pointer reaches the C ABI: detached, fp32, contiguous
+    and 16-byte aligned.  A tensor that is all of that already comes back as it is, without a copy."""
+    return _aligned(x.detach().to(torch.float32).contiguous())
+
+
+def _i32c(x, what):
+    """The same for an index table: any integer dtype becomes contiguous, aligned int32; anything else is refused."""
+    if x.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise L.HodeConfigError("hode: %s must be an integer tensor (got %s)" % (what, x.dtype))
+    return _aligned(x.detach().to(torch.int32).contiguous())
 
 
 def _ptr(x):
@@ -57,7 +72,8 @@ def dose_schedule_index(action):
 
 
 class _RocheFixedGrid(torch.autograd.Function):
-    """h = odeint(RocheODE, y0, t, method) on the gfx950 kernel; backward = discrete adjoint kernel."""
+    """h = odeint(RocheODE, y0, t, method) on the gfx950 kernel; backward = discrete adjoint kernel.
+    Gradients for y0, theta, w, b; none for t, dosage, dose_times (their .grad stays None)."""
 
     @staticmethod
     def forward(ctx, y0, theta, w, b, t, dosage, dose_times, method, ablate, perturb, lanes, check_finite):
@@ -103,7 +119,7 @@ class _RocheFixedGrid(torch.autograd.Function):
         method, ablate, perturb, lanes, has_w = ctx.meta
         lib = L.lib()
         T, B, D = h.shape
-        gh = grad_h.to(torch.float32).contiguous()
+        gh = _f32c(grad_h)
         need_th = bool(ctx.needs_input_grad[1])
         gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)
         gth = torch.zeros(L.N_THETA, device=h.device, dtype=torch.float32)

@@ -10,6 +10,7 @@ import torch
 
 import flow_eager as fe
 import model
+from reference_checks import FLOW_GTOL as GTOL, FLOW_TOL as TOL, close as _close
 from oracle.solvers import odeint as oracle_odeint
 
 pytestmark = pytest.mark.gpu
@@ -47,15 +48,7 @@ def _device_run(mu, lv, u, w, b, noise, s_kl, gz=None, gkl=None):
     return z_out.detach().cpu(), kl.detach().cpu(), [gr.cpu() for gr in grads]
 
 
-def _close(got, ref, rtol, what):
-    ref = ref.to(torch.float64)
-    got = got.to(torch.float64)
-    scale = ref.abs().max().item() + 1e-30
-    err = (got - ref).abs().max().item()
-    assert np.isfinite(err) and err <= rtol * scale, "%s: max err %.3e, scale %.3e" % (what, err, scale)
-
-
-def _check(mu, lv, u, w, b, noise, s_kl, gz, gkl, tol=2e-4, gtol=2e-3, idx=None):
+def _check(mu, lv, u, w, b, noise, s_kl, gz, gkl, tol=TOL, gtol=GTOL, idx=None):
     z, kl, grads = _device_run(mu, lv, u, w, b, noise, s_kl, gz, gkl)
     if idx is not None:  # large B: the fp64 yardstick on a subset of patients (each patient's sums are its own)
         mu, lv, u, w, b = (t[idx] for t in (mu, lv, u, w, b))

@@ -22,10 +22,13 @@ import torch
 
 import kernel_variants as kv
 import neural_real_eager
+from reference_checks import (GRAD_TOL, LSTM_C_TOL, LSTM_H_TOL, NEURAL_DOPRI5_TRAJ_TOL, NEURAL_REAL_GRAD_TOL, READOUT_MLP_GRAD_TOL,
+                              READOUT_TOL, TRAJ_TOL)
 
 pytestmark = pytest.mark.gpu
 
 OBS, ACT, STAT, HIDDEN = 24, 1, 11, 43
+
 
 
 def _dev():
@@ -43,7 +46,7 @@ def _traj_ok(h, ref):
     h, ref = h.detach().double().cpu(), ref.detach().double().cpu()
     assert h.shape == ref.shape
     err = (h - ref).abs().max().item()
-    assert err <= 2e-5 * (1 + ref.abs().max().item()), err
+    assert err <= TRAJ_TOL * (1 + ref.abs().max().item()), err
 
 
 def _family(name):
@@ -110,7 +113,7 @@ def test_neural_real(case):
                                     case["div"], _dev(), seed=case["D"] + case["H"])
     _traj_ok(h, hc)
     for name, g, w in zip(("y0", "w1", "b1", "w2", "b2"), got, want):
-        assert _rel(g, w) < 2e-4, (name, _rel(g, w))
+        assert _rel(g, w) < NEURAL_REAL_GRAD_TOL, (name, _rel(g, w))
 
 
 @pytest.mark.parametrize("kind,D", [("neural", 16), ("2nd", 32)])
@@ -318,7 +321,7 @@ def _ref_finite(case, ref):
             assert torch.isfinite(v).all(), (k, v)
 
 
-def _grad_ok(k, g, r, tol=1e-4):
+def _grad_ok(k, g, r, tol=GRAD_TOL):
     """rel-L2 against the fp64 reference; a NaN the reference has (negative base, _ref_finite) the kernel must have at
     exactly the same positions, and the rest is compared as usual."""
     g, r = g.double().flatten().cpu(), r.double().flatten().cpu()
@@ -636,7 +639,7 @@ def test_neural_dopri5(case, record_property):
     (hr * cot.double()).sum().backward()
     err = (got["h"].double() - hr.detach()).abs().max().item()
     record_property("err_h", err / (1 + hr.abs().max().item()))
-    assert err <= 5e-6 * (1 + hr.abs().max().item()), err
+    assert err <= NEURAL_DOPRI5_TRAJ_TOL * (1 + hr.abs().max().item()), err
     n = f64.ml_net
     for k, a, b in zip(NEURAL_GRADS, got["g"], [y64.grad, n[0].weight.grad, n[0].bias.grad, n[2].weight.grad, n[2].bias.grad]):
         if T == 1:
@@ -741,7 +744,7 @@ def test_lstm(case, monkeypatch, record_property):
     ec = (c.double().cpu() - c64.detach()).abs().max().item()
     record_property("err_h", eh)
     record_property("err_c", ec)
-    assert eh <= 2e-5 and ec <= 5e-5, (eh, ec)
+    assert eh <= LSTM_H_TOL and ec <= LSTM_C_TOL, (eh, ec)
 
 
 # ------------------------------------------------------------------------------------------------------------ readouts
@@ -781,11 +784,11 @@ def test_readout(case, monkeypatch, record_property):
         lik0 = masked_sse_readout(hg.detach(), x.to(dev), m.to(dev), wg.detach(), bg.detach())
     e = abs(lik.item() - ref.item()) / abs(ref.item())
     record_property("err_lik", e)
-    assert e <= 2e-5, e
+    assert e <= READOUT_TOL, e
     for k, g, want in (("gh", hg.grad, hr.grad), ("gw", wg.grad, w64.grad), ("gb", bg.grad, b64.grad)):
         e = _rel(g, want)
         record_property("err_" + k, e)
-        assert e <= 2e-5, (k, e)
+        assert e <= READOUT_TOL, (k, e)
     _lik_same(lik.item(), lik0.item(), record_property)
 
 
@@ -819,5 +822,5 @@ def test_readout_mlp(case, record_property):
     for k, g, want in zip(("gh", "gw1", "gb1", "gw2", "gb2"), [hg.grad] + [q.grad for q in prm], wants):
         e = _rel(g, want)
         record_property("err_" + k, e)
-        assert e <= 3e-5, (k, e)
+        assert e <= READOUT_MLP_GRAD_TOL, (k, e)
     _lik_same(lik.item(), lik0.item(), record_property)

@@ -17,12 +17,12 @@ import pytest
 import torch
 
 import metric_cases as mc
-from oracle.evalmetrics import crps_sorted
+from reference_checks import (CRPS_TOL, MCKL_GRAD_TOL, MCKL_KL_TOL, crps_oracle as _crps_oracle, mckl_scales as _mckl_scales,
+                              mckl_sum_error, within as _within)
 from test_hip_mckl import _reference  # the literal fp64 loop of the reference
 
 pytestmark = pytest.mark.gpu
 
-LN_SQRT_2PI = 0.9189385332046727
 
 
 def _dev():
@@ -61,22 +61,6 @@ def _crps_inputs(c, seed):
     if c["values"] == "zero_spread":
         truth = h[:, 0, :, :obs].clone()
     return h, truth, w, b
-
-
-def _crps_oracle(h, truth, w, b):
-    """fp64 CRPS field (Tn, B, obs) and the per-element tolerance scale."""
-    h64, y = h.double(), truth.double()
-    if w is None:
-        vals = h64[..., :truth.shape[-1]]                                   # (Tn, M, B, obs)
-        extra = 0.0
-    else:
-        w64 = w.double()
-        vals = torch.einsum("tmbd,od->tmbo", h64, w64) + (b.double() if b is not None else 0.0)
-        extra = torch.einsum("tmbd,od->tmbo", h64.abs(), w64.abs()).mean(1) + (b.double().abs() if b is not None else 0.0)
-    ens = vals.permute(0, 2, 3, 1)                                          # (Tn, B, obs, M)
-    ref = torch.from_numpy(crps_sorted(y.numpy(), ens.numpy()))
-    scale = (ens - y[..., None]).abs().mean(-1) + extra
-    return ref, scale
 
 
 def _layout(c, h):
@@ -132,7 +116,7 @@ def test_crps_case(c):
     lib, L = _lib()
     h, truth, w, b = _crps_inputs(c, seed=mc.CRPS_CASES.index(c) + 1)
     ref, scale = _crps_oracle(h, truth, w, b)
-    tol = 2e-5 * scale
+    tol = CRPS_TOL * scale
     store, off, strides = _layout(c, h)
     hdev, tdev = store.to(dev), truth.to(dev)
     wdev = None if w is None else w.to(dev)
@@ -154,7 +138,7 @@ def test_crps_case(c):
             assert bool(((full.double() - (x - truth.double()).abs()).abs() <= tol).all())
     if summed is not None:
         err = (summed.double() - ref.sum(-1)).abs()
-        assert bool((err <= 2e-5 * scale.sum(-1)).all()), float((err / (scale.sum(-1))).max())
+        assert bool((err <= CRPS_TOL * scale.sum(-1)).all()), float((err / (scale.sum(-1))).max())
         if c["values"] == "zero_spread":
             assert bool((summed == 0).all())
 
@@ -233,21 +217,6 @@ def _mckl_inputs(c, seed):
     return mu, lv, noise, zero
 
 
-def _mckl_scales(mu, lv, eps, rate, clamp):
-    """Per element: mean_s of the draw's |log q| + |log p| (plus the constants' magnitudes), of |d/dmu| and of |d/dlv|."""
-    mu, lv, eps = mu.double(), lv.double(), eps.double()
-    sd = torch.exp(0.5 * lv)
-    z = eps * sd + mu
-    pos = z > 0
-    zc = torch.where(pos, z, torch.full_like(z, clamp))
-    log_q = -0.5 * ((zc - mu) / sd) ** 2 - 0.5 * lv - LN_SQRT_2PI
-    log_p = np.log(rate) - rate * zc
-    kl = (log_q.abs() + log_p.abs()).mean(0) + 0.5 * lv.abs() + LN_SQRT_2PI + abs(np.log(rate))
-    gmu = torch.where(pos, torch.full_like(z, rate), (clamp - mu) / sd ** 2).abs().mean(0)
-    glv = 0.5 + torch.where(pos, 0.5 * rate * eps * sd, 0.5 * (clamp - mu) ** 2 / sd ** 2).abs().mean(0)
-    return kl, gmu, glv, pos
-
-
 def _mckl_call(lib, L, mu, lv, noise, rate, clamp, grads):
     dev = mu.device
     rows = mu.numel()
@@ -265,15 +234,6 @@ def _mckl_call(lib, L, mu, lv, noise, rate, clamp, grads):
     return kl.cpu(), gmu.cpu(), glv.cpu()
 
 
-def _within(got, ref, scale, rel, what):
-    err = (got.double() - ref).abs()
-    ok = err <= rel * scale
-    if not bool(ok.all()):
-        i = int(torch.argmax(err / scale.clamp_min(1e-300)))
-        raise AssertionError("%s: element %d got %r want %r (scale %r), %d bad" % (
-            what, i, float(got[i]), float(ref[i]), float(scale[i]), int((~ok).sum())))
-
-
 @pytest.mark.parametrize("c", mc.MCKL_CASES, ids=mc.mckl_id)
 def test_mckl_case(c):
     dev = _dev()
@@ -289,14 +249,14 @@ def test_mckl_case(c):
     assert want, (c["mu"], frac)
     md, lvd, nd = mu.to(dev), lv.to(dev), noise.to(dev)
     kl, gmu, glv = _mckl_call(lib, L, md, lvd, nd, rate, clamp, c["grads"])
-    acc = c["S"] * 2.0 ** -24
-    _within(kl, ref.detach(), s_kl, 2e-5 + acc, "kl")
+    acc = mckl_sum_error(c["S"])
+    _within(kl, ref.detach(), s_kl, MCKL_KL_TOL + acc, "kl")
     if c["grads"] in ("both", "mu"):
-        _within(gmu, mu_r.grad, s_gmu, 1e-5 + acc, "grad_mu")
+        _within(gmu, mu_r.grad, s_gmu, MCKL_GRAD_TOL + acc, "grad_mu")
     else:
         assert bool(torch.isnan(gmu).all())  # no buffer passed: nothing written
     if c["grads"] in ("both", "lv"):
-        _within(glv, lv_r.grad, s_glv, 1e-5 + acc, "grad_log_var")
+        _within(glv, lv_r.grad, s_glv, MCKL_GRAD_TOL + acc, "grad_log_var")
     else:
         assert bool(torch.isnan(glv).all())
     if c["mu"] == "zero":  # z = 0 exactly clamps: d/dmu = (clamp - 0) / 1, not rate
@@ -342,7 +302,7 @@ def test_mckl_wrapper_passes_gradient_buffers_only_when_asked(monkeypatch):
     with torch.no_grad():
         out = mc_kl_exponential(mu.to(dev).requires_grad_(True), lv.to(dev), noise.to(dev), 100.0, clamp)
     assert seen[-1] == (False, False) and not out.requires_grad
-    _within(out.cpu(), ref.detach(), s_kl, 2e-5 + 17 * 2.0 ** -24, "kl (no_grad)")
+    _within(out.cpu(), ref.detach(), s_kl, MCKL_KL_TOL + mckl_sum_error(17), "kl (no_grad)")
 
     for which in ("mu", "lv"):
         md = mu.to(dev).requires_grad_(which == "mu")
@@ -350,10 +310,10 @@ def test_mckl_wrapper_passes_gradient_buffers_only_when_asked(monkeypatch):
         out = mc_kl_exponential(md, lvd, noise.to(dev), 100.0, clamp)
         assert seen[-1] == (True, True)
         (out * wts.float().to(dev)).sum().backward()
-        _within(out.detach().cpu(), ref.detach(), s_kl, 2e-5 + 17 * 2.0 ** -24, "kl")
+        _within(out.detach().cpu(), ref.detach(), s_kl, MCKL_KL_TOL + mckl_sum_error(17), "kl")
         if which == "mu":
             assert lvd.grad is None
-            _within(md.grad.cpu(), mu_r.grad, s_gmu * wts.abs(), 1e-5 + 17 * 2.0 ** -24, "grad_mu")
+            _within(md.grad.cpu(), mu_r.grad, s_gmu * wts.abs(), MCKL_GRAD_TOL + mckl_sum_error(17), "grad_mu")
         else:
             assert md.grad is None
-            _within(lvd.grad.cpu(), lv_r.grad, s_glv * wts.abs(), 1e-5 + 17 * 2.0 ** -24, "grad_log_var")
+            _within(lvd.grad.cpu(), lv_r.grad, s_glv * wts.abs(), MCKL_GRAD_TOL + mckl_sum_error(17), "grad_log_var")
