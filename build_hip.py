@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Build libhode.so and libhode_flow.so (gfx950) in-tree with hipcc: `python build_hip.py [-j N] [--force]`."""
+"""Build libhode.so, libhode_flow.so and libhode_mix.so (gfx950) in-tree with hipcc: `python build_hip.py [-j N] [--force]`."""
 import argparse
 import concurrent.futures as cf
 import hashlib
@@ -17,6 +17,11 @@ FLOW_CSRC = os.path.join(CSRC, "flow")
 FLOW_OBJ = os.path.join(FLOW_CSRC, "build")
 FLOW_OUT = os.path.join(os.path.dirname(OUT), "libhode_flow.so")
 FLOW_HEADER = os.path.join(ROOT, "include", "hode_flow.h")
+# so is the two-model mixture CRPS (C ABI include/hode_mix.h)
+MIX_CSRC = os.path.join(CSRC, "mix")
+MIX_OBJ = os.path.join(MIX_CSRC, "build")
+MIX_OUT = os.path.join(os.path.dirname(OUT), "libhode_mix.so")
+MIX_HEADER = os.path.join(ROOT, "include", "hode_mix.h")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-variable",
          "-Wno-unused-but-set-variable"]
@@ -81,6 +86,23 @@ def flow_source_digest():
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
     h.update(repr((FLAGS, flow_units())).encode().replace(ROOT.encode(), b""))
+    return h.hexdigest()
+
+
+def mix_units():
+    return [("hode_mix", os.path.join(MIX_CSRC, "hode_mix.hip"), [])]
+
+
+def mix_source_digest():
+    """sha256 over everything libhode_mix.so is built from (its sources, its ABI header, the flags); written next to the
+    library, compared by tests/test_mix_host.py."""
+    h = hashlib.sha256()
+    files = [MIX_HEADER] + sorted(
+        os.path.join(MIX_CSRC, f) for f in os.listdir(MIX_CSRC) if f.endswith((".hpp", ".hip", ".h")))
+    for f in files:
+        h.update(os.path.basename(f).encode())
+        h.update(open(f, "rb").read())
+    h.update(repr((FLAGS, mix_units())).encode().replace(ROOT.encode(), b""))
     return h.hexdigest()
 
 
@@ -149,6 +171,7 @@ def build(jobs=7, force=False, verbose=True):
     with open(OUT + ".digest", "w") as f:
         f.write(source_digest() + "\n")
     build_flow(jobs, force, verbose)
+    build_mix(jobs, force, verbose)
     return OUT
 
 
@@ -173,6 +196,29 @@ def build_flow(jobs=1, force=False, verbose=True):
     with open(FLOW_OUT + ".digest", "w") as f:
         f.write(flow_source_digest() + "\n")
     return FLOW_OUT
+
+
+def build_mix(jobs=1, force=False, verbose=True):
+    """libhode_mix.so from csrc/mix/ (objects in csrc/mix/build/)."""
+    os.makedirs(MIX_OBJ, exist_ok=True)
+    us = mix_units()
+    for n, s, e in us:
+        name, dt, err = compile_one(n, s, e, force, 0.0, MIX_OBJ)
+        if verbose and dt:
+            print("  hipcc %-14s %.1fs" % (name, dt), flush=True)
+        if verbose and err.strip():
+            print(err[-2000:], file=sys.stderr)
+    objs = [os.path.join(MIX_OBJ, n + ".o") for n, _, _ in us]
+    if force or not os.path.exists(MIX_OUT) or os.path.getmtime(MIX_OUT) < max(os.path.getmtime(o) for o in objs):
+        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", MIX_OUT] + objs
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("link failed:\n" + r.stderr[-4000:])
+        if verbose:
+            print("  linked", os.path.relpath(MIX_OUT, ROOT), flush=True)
+    with open(MIX_OUT + ".digest", "w") as f:
+        f.write(mix_source_digest() + "\n")
+    return MIX_OUT
 
 
 def build_variant(tag, unit_flags, verbose=True):

@@ -294,3 +294,105 @@ def evaluate_flow(model, data_generator, batch_size, t0, mc_itr=50, real=False):
                             ("cprs_z0", cprs_z0, cprs_z0_sd), ("cprs_x", cprs_x, cprs_x_sd)):
         print("{},{:.4f},{:.4f}".format(name, value, sd))
     return rmse_z0, rmse_z0_sd, cprs_z0, rmse_x, rmse_x_sd, cprs_x
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Two-model evaluation (reference training_utils.py:383-565): the `ensemble2` and `residual` rows of the result tables.
+# The forecast is weight_expert * x_hat_expert + weight_ml * x_hat_ml.  As above, each model's mc_itr draws are ONE decoder
+# call over mc_itr * B latents; the mixture is scored by one `hode_mix_crps` launch that applies both readouts and the
+# weights on the fly (libhode_mix.so, hode/mix.py).
+# ---------------------------------------------------------------------------------------------------------------------
+from hode import mix as _mix_mod
+
+_mixture_crps = _mix_mod.mixture_crps  # tests swap in the CPU oracle here; the product path never does
+
+
+def _forecast_weight(w, t0):
+    """A mixing weight as the scripts pass it -- a Python number or a (T, 1, obs) tensor over the whole grid -- as what
+    ``mixture_crps`` takes for the forecast steps: None for 1, the number, or the (T', obs) table."""
+    if torch.is_tensor(w) and w.dim() == 3:
+        return w[t0:, 0, :]
+    if torch.is_tensor(w):
+        return float(w)
+    return None if w == 1 else w
+
+
+def _mixture_scores(model_expert, model_ml, data, t0, mc_itr, expert_dim, weight_expert, weight_ml):
+    """One test chunk of the two-model evaluation; the sibling of ``_posterior_scores`` with the same return value:
+    (se_z0 (B,), sse_x (T', B), n_x (T', B), crps_z0 (B,) mean over expert dims, crps_x (T', B) mean over obs).
+    z0 errors and ``crps_z0`` are the expert model's alone, as in the reference."""
+    x, a, mask = data["measurements"][:t0], data["actions"][:t0], data["masks"][:t0]
+    z0 = data["latents"][0]
+    encoder_out = model_expert.encoder(x, a, mask)
+    z0_hat = encoder_out[0]
+    x_hat, _ = model_expert.decoder(z0_hat, data["actions"])
+    encoder_out_ml = model_ml.encoder(x, a, mask)
+    x_hat_ml, _ = model_ml.decoder(encoder_out_ml[0], data["actions"])
+    x_hat = (x_hat * weight_expert + x_hat_ml * weight_ml)[t0:, ...]
+    se_z0 = torch.sum((z0[:, :expert_dim] - z0_hat[:, :expert_dim]) ** 2, dim=1)
+    x_test, mask_test = data["measurements"][t0:], data["masks"][t0:]
+    sse_x = torch.sum((x_test - x_hat) ** 2 * mask_test, dim=2)
+    n_x = torch.sum(mask_test, dim=2)
+
+    # ---- posterior ensemble, drawn in the reference's order: per iteration the expert's draw, then the ml model's
+    M = int(mc_itr)
+    B = z0_hat.shape[0]
+    z_e, z_m = [], []
+    for _ in range(M):
+        z_e.append(model_expert.encoder.reparameterize(*encoder_out))
+        z_m.append(model_ml.encoder.reparameterize(*encoder_out_ml))
+    z_e, z_m = torch.stack(z_e, dim=0), torch.stack(z_m, dim=0)                              # (M, B, De), (M, B, Dm)
+    ze_flat, zm_flat = z_e.reshape(M * B, -1), z_m.reshape(M * B, -1)
+    act = data["actions"].repeat(1, M, 1)
+    h_e = model_expert.decoder.latent(ze_flat, act)                                          # (T, M*B, De)
+    h_m = model_ml.decoder.latent(zm_flat, act)                                              # (T, M*B, Dm)
+    crps_x = _mixture_crps(h_e[t0:], h_m[t0:], x_test, M, model_expert.decoder.output_function[0],
+                           model_ml.decoder.output_function[0], weight_e=_forecast_weight(weight_expert, t0),
+                           weight_m=_forecast_weight(weight_ml, t0)) / x_test.shape[2]
+    crps_z0 = _ensemble_crps(ze_flat.unsqueeze(0), z0[:, :expert_dim].unsqueeze(0).contiguous(), M)[0] / expert_dim
+    return se_z0, sse_x, n_x, crps_z0, crps_x
+
+
+def evaluate_ensemble(model_expert, model_ml, data_generator, batch_size, t0, mc_itr=50, weight_expert=1, weight_ml=1):
+    """Reference ``training_utils.evaluate_ensemble`` (:383-486): ``evaluate`` for the forecast
+    ``weight_expert * x_hat_expert + weight_ml * x_hat_ml`` of two models (weights: numbers or (T, 1, obs) tensors).
+    Prints the four ``name,value,sd`` lines and returns ``(rmse_z0, rmse_z0_sd, cprs_z0, rmse_x, rmse_x_sd, cprs_x)``.
+    Kept literally from the reference: ``total_rmse_x`` is NOT cleared of NaN entries (:473-475; ``evaluate`` does clear
+    them), so one test patient without an observation after ``t0`` makes ``rmse_x`` and its spread NaN."""
+    per_chunk = {"se_z0": [], "mse_x": [], "crps_z0": [], "crps_x": []}
+    with torch.no_grad():
+        for chunk in range(data_generator.test_size // batch_size):
+            data = data_generator.get_split("test", batch_size, chunk)
+            se_z0, sse_x, n_x, crps_z0, crps_x = _mixture_scores(model_expert, model_ml, data, t0, mc_itr,
+                                                                 data_generator.expert_dim, weight_expert, weight_ml)
+            per_chunk["se_z0"].append(se_z0.cpu())
+            per_chunk["mse_x"].append((sse_x.sum(dim=0) / n_x.sum(dim=0)).cpu())
+            per_chunk["crps_z0"].append(crps_z0.cpu().numpy())
+            per_chunk["crps_x"].append(crps_x.mean(dim=0).cpu().numpy())
+    rmse_z0, rmse_z0_sd = _rmse_with_bootstrap(torch.cat(per_chunk["se_z0"]))
+    mse_x = torch.cat(per_chunk["mse_x"])
+    rmse_x, rmse_x_sd = torch.sqrt(torch.mean(mse_x)).item(), bootstrap_RMSE(mse_x)
+    cprs_z0, cprs_z0_sd = _mean_with_standard_error(np.concatenate(per_chunk["crps_z0"]))
+    cprs_x, cprs_x_sd = _mean_with_standard_error(np.concatenate(per_chunk["crps_x"]))
+    for name, value, sd in (("rmse_z0", rmse_z0, rmse_z0_sd), ("rmse_x", rmse_x, rmse_x_sd),
+                            ("cprs_z0", cprs_z0, cprs_z0_sd), ("cprs_x", cprs_x, cprs_x_sd)):
+        print("{},{:.4f},{:.4f}".format(name, value, sd))
+    return rmse_z0, rmse_z0_sd, cprs_z0, rmse_x, rmse_x_sd, cprs_x
+
+
+def evaluate_ensemble_horizon(model_expert, model_ml, data_generator, batch_size, t0, mc_itr=10, weight_expert=1,
+                              weight_ml=1):
+    """Reference ``training_utils.evaluate_ensemble_horizon`` (:489-565): the two-model scores per forecast step.
+    Kept literally from the reference: its ``return`` sits inside the chunk loop (:549-565), so the result covers the
+    FIRST test chunk only, and a generator with no full test chunk gives ``None``."""
+    with torch.no_grad():
+        for chunk in range(data_generator.test_size // batch_size):
+            data = data_generator.get_split("test", batch_size, chunk)
+            _, sse_x, n_x, _, crps_x = _mixture_scores(model_expert, model_ml, data, t0, mc_itr, data_generator.expert_dim,
+                                                       weight_expert, weight_ml)
+            mse_x = (sse_x / n_x).cpu()              # (T', B): NaN where a patient has no observation at that step
+            per_step = [_rmse_with_bootstrap(mse_x[i], resample_observed_only=False) for i in range(mse_x.shape[0])]
+            cprs_x, cprs_x_sd = _mean_with_standard_error(crps_x.cpu().numpy(), axis=1)
+            return {"rmse_x": np.array([r for r, _ in per_step], dtype=np.float32),
+                    "rmse_x_sd": np.array([sd for _, sd in per_step]), "cprs_x": cprs_x, "cprs_x_sd": cprs_x_sd}
+    return None
