@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Build libhode.so, libhode_flow.so and libhode_mix.so (gfx950) in-tree with hipcc: `python build_hip.py [-j N] [--force]`."""
+"""Build libhode.so, libhode_flow.so, libhode_mix.so and libhode_blend.so (gfx950) in-tree with hipcc: `python build_hip.py [-j N] [--force]`."""
 import argparse
 import concurrent.futures as cf
 import hashlib
@@ -22,6 +22,11 @@ MIX_CSRC = os.path.join(CSRC, "mix")
 MIX_OBJ = os.path.join(MIX_CSRC, "build")
 MIX_OUT = os.path.join(os.path.dirname(OUT), "libhode_mix.so")
 MIX_HEADER = os.path.join(ROOT, "include", "hode_mix.h")
+# and the real-data two-model scoring kernels (C ABI include/hode_blend.h)
+BLEND_CSRC = os.path.join(CSRC, "blend")
+BLEND_OBJ = os.path.join(BLEND_CSRC, "build")
+BLEND_OUT = os.path.join(os.path.dirname(OUT), "libhode_blend.so")
+BLEND_HEADER = os.path.join(ROOT, "include", "hode_blend.h")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-variable",
          "-Wno-unused-but-set-variable"]
@@ -106,6 +111,23 @@ def mix_source_digest():
     return h.hexdigest()
 
 
+def blend_units():
+    return [("hode_blend", os.path.join(BLEND_CSRC, "hode_blend.hip"), [])]
+
+
+def blend_source_digest():
+    """sha256 over everything libhode_blend.so is built from (its sources, its ABI header, the flags); written next to the
+    library, compared by tests/test_blend_host.py."""
+    h = hashlib.sha256()
+    files = [BLEND_HEADER] + sorted(
+        os.path.join(BLEND_CSRC, f) for f in os.listdir(BLEND_CSRC) if f.endswith((".hpp", ".hip", ".h")))
+    for f in files:
+        h.update(os.path.basename(f).encode())
+        h.update(open(f, "rb").read())
+    h.update(repr((FLAGS, blend_units())).encode().replace(ROOT.encode(), b""))
+    return h.hexdigest()
+
+
 def _deps_newest(obj, src):
     """Newest mtime among the files `obj` was compiled from (the -MD depfile hipcc left next to it), the ABI header and this
     script; None if there is no usable depfile (then the unit is rebuilt)."""
@@ -172,6 +194,7 @@ def build(jobs=7, force=False, verbose=True):
         f.write(source_digest() + "\n")
     build_flow(jobs, force, verbose)
     build_mix(jobs, force, verbose)
+    build_blend(jobs, force, verbose)
     return OUT
 
 
@@ -219,6 +242,29 @@ def build_mix(jobs=1, force=False, verbose=True):
     with open(MIX_OUT + ".digest", "w") as f:
         f.write(mix_source_digest() + "\n")
     return MIX_OUT
+
+
+def build_blend(jobs=1, force=False, verbose=True):
+    """libhode_blend.so from csrc/blend/ (objects in csrc/blend/build/)."""
+    os.makedirs(BLEND_OBJ, exist_ok=True)
+    us = blend_units()
+    for n, s, e in us:
+        name, dt, err = compile_one(n, s, e, force, 0.0, BLEND_OBJ)
+        if verbose and dt:
+            print("  hipcc %-14s %.1fs" % (name, dt), flush=True)
+        if verbose and err.strip():
+            print(err[-2000:], file=sys.stderr)
+    objs = [os.path.join(BLEND_OBJ, n + ".o") for n, _, _ in us]
+    if force or not os.path.exists(BLEND_OUT) or os.path.getmtime(BLEND_OUT) < max(os.path.getmtime(o) for o in objs):
+        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", BLEND_OUT] + objs
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("link failed:\n" + r.stderr[-4000:])
+        if verbose:
+            print("  linked", os.path.relpath(BLEND_OUT, ROOT), flush=True)
+    with open(BLEND_OUT + ".digest", "w") as f:
+        f.write(blend_source_digest() + "\n")
+    return BLEND_OUT
 
 
 def build_variant(tag, unit_flags, verbose=True):

@@ -451,7 +451,13 @@ class EncoderLSTMReal(nn.Module, GaussianReparam):
 
 
 class RocheODEReal(nn.Module):
-    """Real-data hybrid rhs: two small MLPs for x1, x2, expert x3 / Dose2, GRU-ODE block on the rest (model.py:570-657)."""
+    """Real-data hybrid rhs: two small MLPs for x1, x2, expert x3 / Dose2, GRU-ODE block on the rest (model.py:570-657).
+
+    A reproduced quirk: the reference's ``dose_at_time`` sums over dims (0, 2) (model.py:653-657), so EVERY column of the
+    action handed to ``set_action_static`` is added into the dose.  ``run_real_ensemble.py`` and ``run_real_residual.py``
+    call the expert decoder with ``cat([a, s], -1)`` as its action: the published expert forecasts of the ensemble and
+    residual rows had the static covariates added to the dose.  The decay is linear in the dose, so the kernels are handed
+    the column sum; with one column (every other script) the call is what it always was."""
 
     def __init__(self, latent_dim, action_dim, static_dim, hidden_dim, t_max, step_size, device=None, dtype=DTYPE):
         super().__init__()
@@ -539,8 +545,10 @@ class RocheODEReal(nn.Module):
         options.pop("step_t", None)  # ignored by fixed-grid solvers (torchdiffeq only warns)
         theta = torch.stack([self.k_immunity, self.kel, self.kel2])
         wflat, perturb = self.flat_weights(), bool(options.pop("perturb", False))
+        # more than one action column: the reference's sum over dims (0, 2) adds them all into the dose (see the class docstring)
+        dose = self.dosage[..., 0] if self.dosage.shape[-1] == 1 else self.dosage.sum(-1)
         return substep.solve_with_step_size(
-            lambda grid: real.real_solve(y0, theta, wflat, grid, self.dosage[..., 0], self.hidden_dim, method=method, perturb=perturb),
+            lambda grid: real.real_solve(y0, theta, wflat, grid, dose, self.hidden_dim, method=method, perturb=perturb),
             t, step_size)
 
 

@@ -396,3 +396,103 @@ def evaluate_ensemble_horizon(model_expert, model_ml, data_generator, batch_size
             return {"rmse_x": np.array([r for r, _ in per_step], dtype=np.float32),
                     "rmse_x_sd": np.array([sd for _, sd in per_step]), "cprs_x": cprs_x, "cprs_x_sd": cprs_x_sd}
     return None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Real-data experiment (reference experiments/run_real.py:109-137, run_real_ensemble.py:88-154,
+# run_real_residual.py:95-105 and :142-176).  The reference keeps this logic in the scripts' run(); here it is four
+# functions over one fold (a dict with "measurements", "actions", "masks", "statics", each (T, B, .)).  The per-step
+# stacking fit is one `hode_blend_nnls2` launch (the reference: torch -> numpy -> scipy.optimize.nnls per forecast step)
+# and the four-horizon masked error one `hode_blend_horizon_sse` launch that reads every input once (the reference
+# re-forms the blend, the masked squared error and the mask count from full slices once per horizon); libhode_blend.so,
+# hode/blend.py.  Kept literally from the reference: the two-model scripts hand the EXPERT decoder cat([a, s], -1) as its
+# action (model.RocheODEReal adds every column into the dose), the ml decoder the plain action; the fit reads no mask.
+# ---------------------------------------------------------------------------------------------------------------------
+from hode import blend as _blend_mod
+
+_nnls2_weights = _blend_mod.nnls2_weights  # tests swap in the float64 eager forms here; the product path never does
+_horizon_sse = _blend_mod.horizon_sse
+
+REAL_HORIZONS = (6, 12, 24, 72)  # forecast hours of the real-data table (t1_list = 24 + 6, 24 + 12, 24 + 24, 24 + 72)
+
+
+def _fold(data):
+    x, a, mask, s = data["measurements"], data["actions"], data["masks"], data["statics"]
+    return x, a, mask, s, torch.cat([a, s], dim=-1)
+
+
+def _kernel_weight(w):
+    """A mixing weight as ``horizon_sse`` takes it: None for the number 1, else the number or the tensor itself."""
+    if torch.is_tensor(w):
+        return w
+    return None if w == 1 else w
+
+
+def _real_horizon_scores(x_hat, x, mask, t0, horizons, x_e, x_m=None, weight_e=None, weight_m=None):
+    """The scripts' tail: per horizon the per-patient masked mean squared error (patients without an observation
+    dropped), sqrt of its mean, and the bootstrap spread of that (on the CPU: a seeded run resamples alike wherever the
+    forecast was made).  Prints the scripts' ``rmse_x,<t1>,<rmse>,<sd>`` lines."""
+    sse, cnt = _horizon_sse(x_e, x[t0:], mask[t0:], horizons, x_m=x_m, weight_e=weight_e, weight_m=weight_m)
+    per_patient = (sse / cnt).cpu()     # (H, B): NaN where a patient has no observation within the horizon
+    out = {"x_hat": x_hat, "rmse": [], "rmse_sd": [], "mse": []}
+    for h, n in enumerate(horizons):
+        seen = per_patient[h][~torch.isnan(per_patient[h])]
+        rmse = torch.sqrt(torch.mean(seen)).item()
+        rmse_sd = bootstrap_RMSE(seen)
+        print("rmse_x,{:.4f},{:.4f},{:.4f}".format(t0 + n, rmse, rmse_sd))
+        out["rmse"].append(rmse)
+        out["rmse_sd"].append(rmse_sd)
+        out["mse"].append(seen)
+    out["rmse"], out["rmse_sd"] = np.array(out["rmse"]), np.array(out["rmse_sd"])
+    return out
+
+
+def evaluate_real(model, data, t0, horizons=REAL_HORIZONS):
+    """The tail of ``experiments/run_real.py`` (:117-137) on one fold: encode ``x[:t0]``, decode, and per horizon ``n``
+    print ``rmse_x,<t0 + n>,<rmse>,<sd>``.  Returns ``{"x_hat", "rmse" (H,), "rmse_sd" (H,), "mse": H per-patient vectors}``."""
+    x, a, mask, s, a_in = _fold(data)
+    with torch.no_grad():
+        z0_hat = model.encoder(x[:t0], a_in[:t0], mask[:t0])[0]
+        x_hat, _ = model.decoder(z0_hat, a, s)
+        return _real_horizon_scores(x_hat, x, mask, t0, horizons, x_hat)
+
+
+def fit_ensemble_weights(model_expert, model_ml, data, t0):
+    """The stacking fit of ``experiments/run_real_ensemble.py`` (:90-118) on the validation fold: both encoders see the
+    WHOLE fold (not ``x[:t0]``), the expert decoder gets ``cat([a, s], -1)`` as its action and the ml decoder ``a``, and
+    per forecast step the two non-negative weights minimise the unmasked squared error over the step's B * obs entries.
+    Returns ``(weights_e, weights_m)``, each (T', 1, obs) as the script builds them."""
+    x, a, mask, s, a_in = _fold(data)
+    with torch.no_grad():
+        x_hat, _ = model_expert.decoder(model_expert.encoder(x, a_in, mask)[0], a_in, s)
+        x_hat_ml, _ = model_ml.decoder(model_ml.encoder(x, a_in, mask)[0], a, s)
+        w_e, w_m = _nnls2_weights(x_hat, x_hat_ml, x[t0:])
+    obs = x.shape[2]
+    return (w_e.to(x)[:, None, None].expand(-1, 1, obs).contiguous(),
+            w_m.to(x)[:, None, None].expand(-1, 1, obs).contiguous())
+
+
+def residual_targets(model_expert, data, t0, multiplier=0.1):
+    """The residual fold of ``experiments/run_real_residual.py`` (:95-105): a NEW measurement tensor whose rows from
+    ``t0`` on are ``x - multiplier * x_hat_expert`` (the expert encodes the whole fold and is driven by ``cat([a, s], -1)``).
+    The caller assigns it to the fold; the reference mutates the training fold in place."""
+    x, a, mask, s, a_in = _fold(data)
+    with torch.no_grad():
+        x_hat, _ = model_expert.decoder(model_expert.encoder(x, a_in, mask)[0], a_in, s)
+        residual = x.clone()
+        residual[t0:] = residual[t0:] - x_hat * multiplier
+    return residual.detach()
+
+
+def evaluate_real_two_model(model_expert, model_ml, data, t0, weight_expert, weight_ml, horizons=REAL_HORIZONS):
+    """The evaluation of ``experiments/run_real_ensemble.py`` (:120-154; weights: the fitted (T', 1, obs) tensors) and of
+    ``run_real_residual.py`` (:142-176; weights: ``multiplier`` and 1) on the test fold: both encoders see ``x[:t0]``,
+    the forecast is ``x_hat_expert * weight_expert + x_hat_ml * weight_ml``.  Prints and returns what ``evaluate_real``
+    does."""
+    x, a, mask, s, a_in = _fold(data)
+    with torch.no_grad():
+        x_hat1, _ = model_expert.decoder(model_expert.encoder(x[:t0], a_in[:t0], mask[:t0])[0], a_in, s)
+        x_hat2, _ = model_ml.decoder(model_ml.encoder(x[:t0], a_in[:t0], mask[:t0])[0], a, s)
+        x_hat = x_hat1 * weight_expert + x_hat2 * weight_ml
+        return _real_horizon_scores(x_hat, x, mask, t0, horizons, x_hat1, x_m=x_hat2,
+                                    weight_e=_kernel_weight(weight_expert), weight_m=_kernel_weight(weight_ml))
