@@ -1,5 +1,11 @@
 #!/usr/bin/env python
-"""Build libhode.so, libhode_flow.so, libhode_mix.so and libhode_blend.so (gfx950) in-tree with hipcc: `python build_hip.py [-j N] [--force]`."""
+"""Build the gfx950 kernel libraries in-tree with hipcc: `python build_hip.py [-j N] [--force]`.
+
+LIBRARIES is the one table of what is built: libhode.so (C ABI include/hode.h) and the single-unit side libraries
+libhode_flow.so, libhode_mix.so and libhode_blend.so, each with a C ABI header of its own so that its kernels stay out of
+libhode.so.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
+depfile, its flags or this script changed), links each library whose objects are newer than it, and writes
+digest(<library>) next to it as <library>.so.digest; tests and hode/_loader.py compare that stamp with the tree."""
 import argparse
 import concurrent.futures as cf
 import hashlib
@@ -9,24 +15,8 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(ROOT, "hybrid-ode-neurips-2021_amd", "csrc")
-OUT = os.path.join(ROOT, "hybrid-ode-neurips-2021_amd", "hode", "libhode.so")
-OBJ = os.path.join(CSRC, "build")
-# the planar-flow posterior is a library of its own (C ABI include/hode_flow.h): its kernels stay out of libhode.so
-FLOW_CSRC = os.path.join(CSRC, "flow")
-FLOW_OBJ = os.path.join(FLOW_CSRC, "build")
-FLOW_OUT = os.path.join(os.path.dirname(OUT), "libhode_flow.so")
-FLOW_HEADER = os.path.join(ROOT, "include", "hode_flow.h")
-# so is the two-model mixture CRPS (C ABI include/hode_mix.h)
-MIX_CSRC = os.path.join(CSRC, "mix")
-MIX_OBJ = os.path.join(MIX_CSRC, "build")
-MIX_OUT = os.path.join(os.path.dirname(OUT), "libhode_mix.so")
-MIX_HEADER = os.path.join(ROOT, "include", "hode_mix.h")
-# and the real-data two-model scoring kernels (C ABI include/hode_blend.h)
-BLEND_CSRC = os.path.join(CSRC, "blend")
-BLEND_OBJ = os.path.join(BLEND_CSRC, "build")
-BLEND_OUT = os.path.join(os.path.dirname(OUT), "libhode_blend.so")
-BLEND_HEADER = os.path.join(ROOT, "include", "hode_blend.h")
+PKG = "hybrid-ode-neurips-2021_amd"
+CSRC = os.path.join(ROOT, PKG, "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-variable",
          "-Wno-unused-but-set-variable"]
@@ -50,82 +40,63 @@ def units():
     for n in LSTM_TPWS:
         u.append(("hode_lstm_tpw%d" % n, os.path.join(CSRC, "hode_lstm_tpw.hip"), ["-DHODE_LSTM_TPW=%d" % n] + EXTRA_FLAGS["hode_lstm"]))
     for name in ("hode_dopri5", "hode_lstm", "hode_neural", "hode_real", "hode_rk_mf", "hode_readout", "hode_rk_split", "hode_crps", "hode_mckl", "hode_neural_mf", "hode_real_mf", "hode_neural_dopri5", "hode_readout_mlp", "hode_seqdec", "hode_neural_real_mf"):
-        src = os.path.join(CSRC, name + ".hip")
-        if os.path.exists(src):
-            u.append((name, src, EXTRA_FLAGS.get(name, [])))
+        u.append((name, os.path.join(CSRC, name + ".hip"), EXTRA_FLAGS.get(name, [])))
     return u
 
 
-def newest_dep():
-    ts = [os.path.getmtime(os.path.join(ROOT, "include", "hode.h")), os.path.getmtime(__file__)]
-    for f in os.listdir(CSRC):
-        if f.endswith((".hpp", ".hip", ".h")):
-            ts.append(os.path.getmtime(os.path.join(CSRC, f)))
-    return max(ts)
+class Library:
+    """One row of LIBRARIES: the file name of the library in hode/ and what it is built from.  `src_dir`, `header` and
+    `extra` are relative to the repository root and use "/", so that digest() is the same wherever the tree lives.
+    `extra` names what the units include from outside `src_dir` and the ABI header; `units` is a callable returning
+    [(unit name, absolute source path, extra flags)]; objects go to <src_dir>/build."""
+
+    def __init__(self, name, src_dir, header, extra, units):
+        self.name, self.src_dir, self.header, self.extra, self.units = name, src_dir, header, tuple(extra), units
+        self.out = os.path.join(ROOT, PKG, "hode", name)
+        self.obj = os.path.join(ROOT, src_dir, "build")
+
+
+def _side(name, *extra):
+    """A side library: csrc/<name>/hode_<name>.hip alone, with the shared host error helper."""
+    d = PKG + "/csrc/" + name
+    unit = ("hode_" + name, os.path.join(ROOT, d, "hode_%s.hip" % name), [])
+    return Library("libhode_%s.so" % name, d, "include/hode_%s.h" % name, extra + (PKG + "/csrc/hode_side_error.hpp",),
+                   lambda: [unit])
+
+
+#: every library, by file name
+LIBRARIES = {lib.name: lib for lib in (
+    Library("libhode.so", PKG + "/csrc", "include/hode.h", (), units),
+    _side("flow", PKG + "/csrc/hode_common.hpp"),   # the planar-flow posterior
+    _side("mix"),                                   # the two-model mixture CRPS
+    _side("blend"),                                 # the real-data two-model scoring kernels
+)}
+OUT = LIBRARIES["libhode.so"].out
+OBJ = LIBRARIES["libhode.so"].obj
+
+
+def digest_files(lib):
+    """What digest(lib) reads, relative to the repository root: the ABI header, `extra`, every source in `src_dir`."""
+    lib = LIBRARIES[lib]
+    own = [lib.src_dir + "/" + f for f in os.listdir(os.path.join(ROOT, lib.src_dir)) if f.endswith((".hpp", ".hip", ".h"))]
+    return sorted({lib.header, *lib.extra, *own})
+
+
+def digest(lib):
+    """sha256 over everything the library is built from: the files of digest_files() under their relative names, the
+    flags and the units.  Written next to the library after a build and compared by the tests and by the loader, so a
+    library left over from other sources (e.g. after `git checkout`) is caught."""
+    h = hashlib.sha256()
+    for f in digest_files(lib):
+        h.update(f.encode())
+        h.update(open(os.path.join(ROOT, f), "rb").read())
+    us = [(n, os.path.relpath(s, ROOT).replace(os.sep, "/"), e) for n, s, e in LIBRARIES[lib].units()]
+    h.update(repr((FLAGS, us)).encode())
+    return h.hexdigest()
 
 
 def source_digest():
-    """sha256 over everything the library is built from (sources, ABI header, flags).  Written next to libhode.so after a
-    build; tests/test_abi.py compares, so a library left over from other sources (e.g. after `git checkout`) is caught."""
-    h = hashlib.sha256()
-    files = [os.path.join(ROOT, "include", "hode.h")] + sorted(
-        os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".hip", ".h")))
-    for f in files:
-        h.update(os.path.basename(f).encode())
-        h.update(open(f, "rb").read())
-    h.update(repr((FLAGS, sorted(EXTRA_FLAGS.items()), DP_FLAGS, RK_DIMS, DP_DIMS, LSTM_TPWS)).encode())
-    return h.hexdigest()
-
-
-def flow_units():
-    return [("hode_flow", os.path.join(FLOW_CSRC, "hode_flow.hip"), [])]
-
-
-def flow_source_digest():
-    """sha256 over everything libhode_flow.so is built from (its sources, its ABI header, the shared device helpers, the
-    flags); written next to the library, compared by tests/test_flow_host.py."""
-    h = hashlib.sha256()
-    files = [FLOW_HEADER, os.path.join(CSRC, "hode_common.hpp")] + sorted(
-        os.path.join(FLOW_CSRC, f) for f in os.listdir(FLOW_CSRC) if f.endswith((".hpp", ".hip", ".h")))
-    for f in files:
-        h.update(os.path.basename(f).encode())
-        h.update(open(f, "rb").read())
-    h.update(repr((FLAGS, flow_units())).encode().replace(ROOT.encode(), b""))
-    return h.hexdigest()
-
-
-def mix_units():
-    return [("hode_mix", os.path.join(MIX_CSRC, "hode_mix.hip"), [])]
-
-
-def mix_source_digest():
-    """sha256 over everything libhode_mix.so is built from (its sources, its ABI header, the flags); written next to the
-    library, compared by tests/test_mix_host.py."""
-    h = hashlib.sha256()
-    files = [MIX_HEADER] + sorted(
-        os.path.join(MIX_CSRC, f) for f in os.listdir(MIX_CSRC) if f.endswith((".hpp", ".hip", ".h")))
-    for f in files:
-        h.update(os.path.basename(f).encode())
-        h.update(open(f, "rb").read())
-    h.update(repr((FLAGS, mix_units())).encode().replace(ROOT.encode(), b""))
-    return h.hexdigest()
-
-
-def blend_units():
-    return [("hode_blend", os.path.join(BLEND_CSRC, "hode_blend.hip"), [])]
-
-
-def blend_source_digest():
-    """sha256 over everything libhode_blend.so is built from (its sources, its ABI header, the flags); written next to the
-    library, compared by tests/test_blend_host.py."""
-    h = hashlib.sha256()
-    files = [BLEND_HEADER] + sorted(
-        os.path.join(BLEND_CSRC, f) for f in os.listdir(BLEND_CSRC) if f.endswith((".hpp", ".hip", ".h")))
-    for f in files:
-        h.update(os.path.basename(f).encode())
-        h.update(open(f, "rb").read())
-    h.update(repr((FLAGS, blend_units())).encode().replace(ROOT.encode(), b""))
-    return h.hexdigest()
+    return digest("libhode.so")
 
 
 def _deps_newest(obj, src):
@@ -148,7 +119,7 @@ def _deps_newest(obj, src):
     return max(ts)
 
 
-def compile_one(name, src, extra, force, dep_time, obj_dir=OBJ):
+def compile_one(name, src, extra, force, obj_dir=OBJ):
     obj = os.path.join(obj_dir, name + ".o")
     flags_txt = " ".join(FLAGS + extra)
     stamp = obj[:-2] + ".flags"
@@ -170,101 +141,34 @@ def compile_one(name, src, extra, force, dep_time, obj_dir=OBJ):
     return name, time.time() - t0, r.stderr
 
 
+def link(out, objs):
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", out] + objs,
+                       capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("link failed:\n" + r.stderr[-4000:])
+
+
 def build(jobs=7, force=False, verbose=True):
-    os.makedirs(OBJ, exist_ok=True)
-    dep = newest_dep()
-    us = units()
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
-        futs = [ex.submit(compile_one, n, s, e, force, dep) for n, s, e in us]
+        futs = []
+        for lib in LIBRARIES.values():
+            os.makedirs(lib.obj, exist_ok=True)
+            futs += [ex.submit(compile_one, n, s, e, force, lib.obj) for n, s, e in lib.units()]
         for f in futs:
             name, dt, err = f.result()
             if verbose and dt:
                 print("  hipcc %-14s %.1fs" % (name, dt), flush=True)
             if verbose and err.strip():
                 print(err[-2000:], file=sys.stderr)
-    objs = [os.path.join(OBJ, n + ".o") for n, _, _ in us]
-    if force or not os.path.exists(OUT) or os.path.getmtime(OUT) < max(os.path.getmtime(o) for o in objs):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", OUT] + objs
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("link failed:\n" + r.stderr[-4000:])
-        if verbose:
-            print("  linked", os.path.relpath(OUT, ROOT), flush=True)
-    with open(OUT + ".digest", "w") as f:
-        f.write(source_digest() + "\n")
-    build_flow(jobs, force, verbose)
-    build_mix(jobs, force, verbose)
-    build_blend(jobs, force, verbose)
+    for lib in LIBRARIES.values():
+        objs = [os.path.join(lib.obj, n + ".o") for n, _, _ in lib.units()]
+        if force or not os.path.exists(lib.out) or os.path.getmtime(lib.out) < max(os.path.getmtime(o) for o in objs):
+            link(lib.out, objs)
+            if verbose:
+                print("  linked", os.path.relpath(lib.out, ROOT), flush=True)
+        with open(lib.out + ".digest", "w") as f:
+            f.write(digest(lib.name) + "\n")
     return OUT
-
-
-def build_flow(jobs=1, force=False, verbose=True):
-    """libhode_flow.so from csrc/flow/ (objects in csrc/flow/build/)."""
-    os.makedirs(FLOW_OBJ, exist_ok=True)
-    us = flow_units()
-    for n, s, e in us:
-        name, dt, err = compile_one(n, s, e, force, 0.0, FLOW_OBJ)
-        if verbose and dt:
-            print("  hipcc %-14s %.1fs" % (name, dt), flush=True)
-        if verbose and err.strip():
-            print(err[-2000:], file=sys.stderr)
-    objs = [os.path.join(FLOW_OBJ, n + ".o") for n, _, _ in us]
-    if force or not os.path.exists(FLOW_OUT) or os.path.getmtime(FLOW_OUT) < max(os.path.getmtime(o) for o in objs):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", FLOW_OUT] + objs
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("link failed:\n" + r.stderr[-4000:])
-        if verbose:
-            print("  linked", os.path.relpath(FLOW_OUT, ROOT), flush=True)
-    with open(FLOW_OUT + ".digest", "w") as f:
-        f.write(flow_source_digest() + "\n")
-    return FLOW_OUT
-
-
-def build_mix(jobs=1, force=False, verbose=True):
-    """libhode_mix.so from csrc/mix/ (objects in csrc/mix/build/)."""
-    os.makedirs(MIX_OBJ, exist_ok=True)
-    us = mix_units()
-    for n, s, e in us:
-        name, dt, err = compile_one(n, s, e, force, 0.0, MIX_OBJ)
-        if verbose and dt:
-            print("  hipcc %-14s %.1fs" % (name, dt), flush=True)
-        if verbose and err.strip():
-            print(err[-2000:], file=sys.stderr)
-    objs = [os.path.join(MIX_OBJ, n + ".o") for n, _, _ in us]
-    if force or not os.path.exists(MIX_OUT) or os.path.getmtime(MIX_OUT) < max(os.path.getmtime(o) for o in objs):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", MIX_OUT] + objs
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("link failed:\n" + r.stderr[-4000:])
-        if verbose:
-            print("  linked", os.path.relpath(MIX_OUT, ROOT), flush=True)
-    with open(MIX_OUT + ".digest", "w") as f:
-        f.write(mix_source_digest() + "\n")
-    return MIX_OUT
-
-
-def build_blend(jobs=1, force=False, verbose=True):
-    """libhode_blend.so from csrc/blend/ (objects in csrc/blend/build/)."""
-    os.makedirs(BLEND_OBJ, exist_ok=True)
-    us = blend_units()
-    for n, s, e in us:
-        name, dt, err = compile_one(n, s, e, force, 0.0, BLEND_OBJ)
-        if verbose and dt:
-            print("  hipcc %-14s %.1fs" % (name, dt), flush=True)
-        if verbose and err.strip():
-            print(err[-2000:], file=sys.stderr)
-    objs = [os.path.join(BLEND_OBJ, n + ".o") for n, _, _ in us]
-    if force or not os.path.exists(BLEND_OUT) or os.path.getmtime(BLEND_OUT) < max(os.path.getmtime(o) for o in objs):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", BLEND_OUT] + objs
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("link failed:\n" + r.stderr[-4000:])
-        if verbose:
-            print("  linked", os.path.relpath(BLEND_OUT, ROOT), flush=True)
-    with open(BLEND_OUT + ".digest", "w") as f:
-        f.write(blend_source_digest() + "\n")
-    return BLEND_OUT
 
 
 def build_variant(tag, unit_flags, verbose=True):
@@ -287,10 +191,7 @@ def build_variant(tag, unit_flags, verbose=True):
         else:
             objs.append(os.path.join(OBJ, name + ".o"))
     out = os.path.join(os.path.dirname(OUT), "libhode_%s.so" % tag)
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", out] + objs,
-                       capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("link failed:\n" + r.stderr[-4000:])
+    link(out, objs)
     return out
 
 

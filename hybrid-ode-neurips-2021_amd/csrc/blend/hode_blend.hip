@@ -16,10 +16,8 @@
 // Deterministic: fixed summation order, no atomics.  A library of its own (C ABI: include/hode_blend.h).
 #include <hip/hip_runtime.h>
 
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "../../../include/hode_blend.h"
+#include "../hode_side_error.hpp"
 
 namespace hode_blend {
 
@@ -28,16 +26,8 @@ constexpr int kWave = 64;
 constexpr int kWaveRows = 256;       // steps of at most this many entries are reduced by one wave each
 constexpr double kDecreaseSlack = 1e-9;  // relative slack of solve2's check of the unconstrained candidate
 
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-static int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
+using hode_side::fail;
+using hode_side::launch_fail;
 
 struct Nnls2Args {
   const float* __restrict__ xe;
@@ -178,17 +168,11 @@ __global__ __launch_bounds__(kThreads) void horizon_sse_kernel(HorizonArgs a) {
   }
 }
 
-static int launch_fail(hipError_t e, const char* what) {
-  if (e == hipSuccess) return 0;
-  fail((int)e, "%s: %s", what, hipGetErrorString(e));
-  return (int)e;
-}
-
 }  // namespace hode_blend
 
 extern "C" int hode_blend_version(void) { return HODE_BLEND_ABI_VERSION; }
 
-extern "C" const char* hode_blend_last_error_string(void) { return hode_blend::g_err; }
+extern "C" const char* hode_blend_last_error_string(void) { return hode_side::g_err; }
 
 extern "C" int hode_blend_nnls2(const hode_blend_nnls2_desc* d, void* stream) {
   using namespace hode_blend;

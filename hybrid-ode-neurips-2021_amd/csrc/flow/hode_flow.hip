@@ -14,11 +14,9 @@
 // are bit-identical.  The u_hat reparameterisation's backward runs once per patient and flow after the last sample.
 #include <hip/hip_runtime.h>
 
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "../../../include/hode_flow.h"
 #include "../hode_common.hpp"
+#include "../hode_side_error.hpp"
 
 namespace hode_flow {
 
@@ -33,16 +31,8 @@ constexpr float kLogRate = 4.605170185988092f;  // log 100
 constexpr float kRate = 100.0f;
 constexpr int kLdsLimit = 64 * 1024;
 
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-static int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
+using hode_side::fail;
+using hode_side::launch_fail;
 
 struct FlowArgs {
   const float* __restrict__ mu;
@@ -357,12 +347,6 @@ static FlowArgs args_of(const hode_flow_desc* d) {
   return a;
 }
 
-static int launch_fail(hipError_t e, const char* what) {
-  if (e == hipSuccess) return 0;
-  fail((int)e, "%s: %s", what, hipGetErrorString(e));
-  return (int)e;
-}
-
 template <int DT>
 static int launch(FlowArgs a, bool bwd, hipStream_t st) {
   a.L = lanes_per_patient(a.B, a.S, a.K, DT);
@@ -389,7 +373,7 @@ static int dispatch(const FlowArgs& a, bool bwd, hipStream_t st) {
 
 extern "C" int hode_flow_version(void) { return HODE_FLOW_ABI_VERSION; }
 
-extern "C" const char* hode_flow_last_error_string(void) { return hode_flow::g_err; }
+extern "C" const char* hode_flow_last_error_string(void) { return hode_side::g_err; }
 
 extern "C" int hode_flow_fwd(const hode_flow_desc* d, void* stream) {
   using namespace hode_flow;

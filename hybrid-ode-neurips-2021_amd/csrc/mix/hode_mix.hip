@@ -16,10 +16,8 @@
 // A library of its own (C ABI: include/hode_mix.h): its kernel stays out of libhode.so.
 #include <hip/hip_runtime.h>
 
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "../../../include/hode_mix.h"
+#include "../hode_side_error.hpp"
 
 namespace hode_mix {
 
@@ -29,16 +27,8 @@ constexpr size_t kMixPackLds = 64 * 1024;            // rows are packed only whi
 constexpr size_t kMixLdsLimit = 160 * 1024;          // LDS of a gfx950 workgroup
 constexpr size_t kMixStaticLds = kMixThreads * sizeof(float);  // the kernel's static block (per-thread scores)
 
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-static int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
+using hode_side::fail;
+using hode_side::launch_fail;
 
 struct MixArgs {
   const float* __restrict__ he;
@@ -150,17 +140,11 @@ __global__ __launch_bounds__(kMixThreads) void mix_crps_kernel(MixArgs a) {
   }
 }
 
-static int launch_fail(hipError_t e, const char* what) {
-  if (e == hipSuccess) return 0;
-  fail((int)e, "%s: %s", what, hipGetErrorString(e));
-  return (int)e;
-}
-
 }  // namespace hode_mix
 
 extern "C" int hode_mix_version(void) { return HODE_MIX_ABI_VERSION; }
 
-extern "C" const char* hode_mix_last_error_string(void) { return hode_mix::g_err; }
+extern "C" const char* hode_mix_last_error_string(void) { return hode_side::g_err; }
 
 extern "C" int hode_mix_crps(const hode_mix_crps_desc* d, void* stream) {
   using namespace hode_mix;

@@ -4,13 +4,8 @@ when the library is missing, stale or of another ABI version."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 
-from ._lib import HodeConfigError
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
-_LIB_NAME = "libhode_blend.so"
+from ._loader import HodeConfigError, Library  # noqa: F401
 
 HODE_BLEND_ABI_VERSION = 1
 MAX_OBS, MAX_HORIZONS = 128, 8
@@ -44,58 +39,9 @@ EXPORTS = (
     ("hode_blend_horizon_sse", C.c_int, (C.POINTER(HorizonDesc), C.c_void_p)),
 )
 
-_lib = None
-
-
-def library_path() -> str:
-    return os.environ.get("HODE_BLEND_LIBRARY", os.path.join(_HERE, _LIB_NAME))
-
-
-def _check_digest(path):
-    """A library left over from other sources (e.g. after `git checkout`) is refused when the sources are there to compare."""
-    stamp = path + ".digest"
-    if "HODE_BLEND_LIBRARY" in os.environ or not os.path.exists(stamp) or not os.path.exists(os.path.join(_ROOT, "build_hip.py")):
-        return
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("_hode_build_hip", os.path.join(_ROOT, "build_hip.py"))
-    mod = importlib.util.module_from_spec(spec)
-    try:
-        spec.loader.exec_module(mod)
-        want = mod.blend_source_digest()
-    except OSError:
-        return  # sources not shipped with the package
-    if open(stamp).read().strip() != want:
-        raise HodeConfigError("hode: %s is stale (its digest does not match csrc/blend/ and include/hode_blend.h) -- "
-                              "rebuild with `python build_hip.py`" % path)
-
-
-def lib():
-    """Load (once) and return the ctypes handle; raises HodeConfigError if the library is absent, stale or of another ABI."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    path = library_path()
-    if not os.path.exists(path):
-        raise HodeConfigError(
-            "hode: %s not found -- build it with `python build_hip.py` (hipcc --offload-arch=gfx950). "
-            "There is no CPU fallback for the blend kernels on the device." % path
-        )
-    _check_digest(path)
-    handle = C.CDLL(path)
-    for name, restype, argtypes in EXPORTS:
-        fn = getattr(handle, name)
-        fn.restype = restype
-        fn.argtypes = list(argtypes)
-    if handle.hode_blend_version() != HODE_BLEND_ABI_VERSION:
-        raise HodeConfigError("hode: blend ABI version %d != expected %d" % (handle.hode_blend_version(), HODE_BLEND_ABI_VERSION))
-    _lib = handle
-    return _lib
-
-
-def check(code: int, what: str):
-    if code != 0:
-        msg = lib().hode_blend_last_error_string().decode("utf-8", "replace")
-        raise HodeConfigError("%s failed (code %d): %s" % (what, code, msg))
+LIBRARY = Library("libhode_blend.so", "HODE_BLEND_LIBRARY", EXPORTS, "hode_blend_version", "hode_blend_last_error_string",
+                   HODE_BLEND_ABI_VERSION, "the blend kernels on the device", check_digest=True)
+lib, library_path, check = LIBRARY.load, LIBRARY.path, LIBRARY.check
 
 
 def new_desc(cls):

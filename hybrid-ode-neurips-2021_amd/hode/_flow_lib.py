@@ -4,12 +4,8 @@ when the library is missing, stale or of another ABI version."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 
-from ._lib import HodeConfigError
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB_NAME = "libhode_flow.so"
+from ._loader import HodeConfigError, Library  # noqa: F401
 
 HODE_FLOW_ABI_VERSION = 1
 MAX_LATENT, MAX_FLOWS, MAX_SAMPLES = 32, 16, 256
@@ -35,39 +31,9 @@ EXPORTS = (
     ("hode_flow_bwd", C.c_int, (C.POINTER(FlowDesc), C.c_void_p)),
 )
 
-_lib = None
-
-
-def library_path() -> str:
-    return os.environ.get("HODE_FLOW_LIBRARY", os.path.join(_HERE, _LIB_NAME))
-
-
-def lib():
-    """Load (once) and return the ctypes handle; raises HodeConfigError if the library is absent or of another ABI."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    path = library_path()
-    if not os.path.exists(path):
-        raise HodeConfigError(
-            "hode: %s not found -- build it with `python build_hip.py` (hipcc --offload-arch=gfx950). "
-            "There is no CPU fallback for the flow posterior on the device." % path
-        )
-    handle = C.CDLL(path)
-    for name, restype, argtypes in EXPORTS:
-        fn = getattr(handle, name)
-        fn.restype = restype
-        fn.argtypes = list(argtypes)
-    if handle.hode_flow_version() != HODE_FLOW_ABI_VERSION:
-        raise HodeConfigError("hode: flow ABI version %d != expected %d" % (handle.hode_flow_version(), HODE_FLOW_ABI_VERSION))
-    _lib = handle
-    return _lib
-
-
-def check(code: int, what: str):
-    if code != 0:
-        msg = lib().hode_flow_last_error_string().decode("utf-8", "replace")
-        raise HodeConfigError("%s failed (code %d): %s" % (what, code, msg))
+LIBRARY = Library("libhode_flow.so", "HODE_FLOW_LIBRARY", EXPORTS, "hode_flow_version", "hode_flow_last_error_string",
+                   HODE_FLOW_ABI_VERSION, "the flow posterior on the device", check_digest=True)
+lib, library_path, check = LIBRARY.load, LIBRARY.path, LIBRARY.check
 
 
 def new_desc() -> FlowDesc:

@@ -3,10 +3,8 @@
 from __future__ import annotations
 
 import ctypes as C
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB_NAME = "libhode.so"
+from ._loader import HodeConfigError, Library  # noqa: F401
 
 HODE_ABI_VERSION = 1
 
@@ -24,13 +22,6 @@ class HodeError(RuntimeError):
     """NUMERICAL failure of a solve, reported by the kernels' status word: non-finite state, dt underflow, step bound
     exceeded.  A RuntimeError so that the reference's ``except RuntimeError`` around ``model.loss``
     (training_utils.py:43-47) keeps ending a diverged restart."""
-
-
-class HodeConfigError(Exception):
-    """Everything that is NOT the numerics' fault: libhode.so missing / stale / ABI mismatch, an argument error or
-    unsupported shape reported by an entry point (HODE_E_*), a HIP launch error, CPU tensors handed to the GPU-only
-    path.  Deliberately not a RuntimeError: the mirrored training loop must not mistake it for solver divergence,
-    print it, save the untrained model and carry on."""
 
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -155,39 +146,11 @@ EXPORTS = (
     ("hode_seqdec_bwd", C.c_int, (C.POINTER(SeqdecDesc), C.c_void_p)),
 )
 
-_lib = None
-
-
-def library_path() -> str:
-    return os.environ.get("HODE_LIBRARY", os.path.join(_HERE, _LIB_NAME))
-
-
-def lib():
-    """Load (once) and return the ctypes handle; raises HodeConfigError if the library is absent or stale."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    path = library_path()
-    if not os.path.exists(path):
-        raise HodeConfigError(
-            "hode: %s not found -- build it with `python build_hip.py` (hipcc --offload-arch=gfx950). "
-            "There is no CPU fallback for the solver path." % path
-        )
-    handle = C.CDLL(path)
-    for name, restype, argtypes in EXPORTS:
-        fn = getattr(handle, name)  # AttributeError if the symbol is missing
-        fn.restype = restype
-        fn.argtypes = list(argtypes)
-    if handle.hode_version() != HODE_ABI_VERSION:
-        raise HodeConfigError("hode: ABI version %d != expected %d" % (handle.hode_version(), HODE_ABI_VERSION))
-    _lib = handle
-    return _lib
-
-
-def check(code: int, what: str):
-    if code != 0:
-        msg = lib().hode_last_error_string().decode("utf-8", "replace")
-        raise HodeConfigError("%s failed (code %d): %s" % (what, code, msg))
+# no digest check at load: the probe tools load experiment builds (HODE_DP_FLAGS, HODE_LSTM_FLAGS, HODE_SPLIT_FLAGS) without
+# those variables set, so their digest legitimately differs; tests/test_abi.py guards the product build
+LIBRARY = Library("libhode.so", "HODE_LIBRARY", EXPORTS, "hode_version", "hode_last_error_string", HODE_ABI_VERSION,
+                   "the solver path", check_digest=False)
+lib, library_path, check = LIBRARY.load, LIBRARY.path, LIBRARY.check
 
 
 def new_solve_desc() -> SolveDesc:

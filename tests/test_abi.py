@@ -1,35 +1,25 @@
 """CPU-only checks of the C-ABI boundary: the library loads, exports every symbol include/hode.h declares, the ctypes
 mirrors have the C struct sizes, and argument errors are reported (no kernel is launched without a GPU)."""
-import ctypes
 import os
-import re
 import subprocess
 import sys
 
 import pytest
 
+import abi_checks
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hode.h")
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import hode
-    if not os.path.exists(hode.library_path()):
-        import build_hip
-        build_hip.build(verbose=False)
-    return hode.lib()
-
-
-def _declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(hode_[a-z0-9_]+)\s*\(", src)))
+    from hode import _lib as L
+    return abi_checks.built(L.LIBRARY)
 
 
 def test_header_functions_are_exported_and_bound(lib):
     from hode import _lib as L
-    declared = _declared_functions()
+    declared = abi_checks.declared_functions("hode.h", "hode_")
     assert {"hode_rk_fwd", "hode_rk_bwd", "hode_dopri5_fwd", "hode_dopri5_bwd", "hode_lstm_fwd", "hode_lstm_bwd",
             "hode_version", "hode_last_error_string", "hode_workspace_bytes"} <= set(declared)
     bound = {name for name, _, _ in L.EXPORTS}
@@ -41,18 +31,10 @@ def test_header_functions_are_exported_and_bound(lib):
 
 def test_struct_sizes_match_the_c_header(tmp_path):
     from hode import _lib as L
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include "%s"\nint main(){printf("%%zu %%zu %%zu %%zu %%zu %%zu %%zu %%zu %%zu\\n", sizeof(hode_solve_desc), '
-                   'sizeof(hode_lstm_desc), offsetof(hode_solve_desc, workspace), sizeof(hode_readout_desc), '
-                   'sizeof(hode_crps_desc), offsetof(hode_crps_desc, truth), sizeof(hode_mckl_desc), sizeof(hode_readout_mlp_desc), '
-                   'sizeof(hode_dopri5_init_record));return 0;}\n' % HEADER)
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", str(src), "-o", str(exe)])
-    a, b, c, r, k, ko, mk, rm, ir = (int(v) for v in subprocess.check_output([str(exe)]).split())
-    assert ctypes.sizeof(L.SolveDesc) == a and ctypes.sizeof(L.LstmDesc) == b
-    assert L.SolveDesc.workspace.offset == c
-    assert ctypes.sizeof(L.ReadoutDesc) == r and ctypes.sizeof(L.CrpsDesc) == k and L.CrpsDesc.truth.offset == ko
-    assert ctypes.sizeof(L.McKlDesc) == mk and ctypes.sizeof(L.ReadoutMlpDesc) == rm and ctypes.sizeof(L.Dopri5InitRecord) == ir
+    for c_type, mirror in (("hode_solve_desc", L.SolveDesc), ("hode_lstm_desc", L.LstmDesc), ("hode_readout_desc", L.ReadoutDesc),
+                           ("hode_crps_desc", L.CrpsDesc), ("hode_mckl_desc", L.McKlDesc), ("hode_readout_mlp_desc", L.ReadoutMlpDesc),
+                           ("hode_dopri5_init_record", L.Dopri5InitRecord), ("hode_seqdec_desc", L.SeqdecDesc)):
+        abi_checks.assert_c_layout("hode.h", c_type, mirror, tmp_path)
 
 
 def test_argument_errors_do_not_launch(lib):
@@ -128,7 +110,5 @@ def test_library_was_built_from_the_sources_in_the_tree():
     """build_hip.py stamps libhode.so with a digest of the sources, header and flags it was built from; a library left
     over from other sources (an experiment reverted with `git checkout`, a forgotten rebuild) must not pass as current."""
     import build_hip
-    stamp = build_hip.OUT + ".digest"
     assert os.path.exists(build_hip.OUT), "libhode.so missing: run `python build_hip.py`"
-    assert os.path.exists(stamp), "libhode.so has no source digest: rebuild with `python build_hip.py`"
-    assert open(stamp).read().strip() == build_hip.source_digest(), "libhode.so is stale: run `python build_hip.py`"
+    abi_checks.assert_digest_current("libhode.so")

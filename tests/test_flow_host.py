@@ -2,23 +2,21 @@
 against the reference's own numbers (G11, tests/golden/make_golden_flow.py), the float64 restatement (flow_eager)
 against G11, the domain refusals, libhode_flow.so's C ABI, and the guard that every compiled flow kernel is reached by a
 case of the GPU test table."""
-import ctypes
 import glob
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+import abi_checks
 import flow_eager as fe
 import model
 from oracle.solvers import odeint as oracle_odeint
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hode_flow.h")
 FLOW_BUILD = os.path.join(ROOT, "hybrid-ode-neurips-2021_amd", "csrc", "flow", "build")
 CPU = torch.device("cpu")
 OBS, ACT, HIDDEN = 20, 1, 40
@@ -178,34 +176,24 @@ def test_domain_refusals():
 @pytest.fixture(scope="module")
 def flow_lib():
     from hode import _flow_lib as F
-    if not os.path.exists(F.library_path()):
-        import build_hip
-        build_hip.build(verbose=False)
-    return F.lib()
+    return abi_checks.built(F.LIBRARY)
 
 
 def test_header_functions_are_exported_and_bound(flow_lib):
     from hode import _flow_lib as F
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = set(re.findall(r"\b(hode_flow_[a-z0-9_]+)\s*\(", src))
+    declared = abi_checks.declared_functions("hode_flow.h", "hode_flow_")
     assert declared == {name for name, _, _ in F.EXPORTS}
     for name in declared:
         assert getattr(flow_lib, name) is not None
     assert flow_lib.hode_flow_version() == F.HODE_FLOW_ABI_VERSION
-    consts = dict(re.findall(r"#define (HODE_FLOW_MAX_[A-Z]+) (\d+)", src))
+    consts = dict(re.findall(r"#define (HODE_FLOW_MAX_[A-Z]+) (\d+)", abi_checks.header_text("hode_flow.h")))
     assert (int(consts["HODE_FLOW_MAX_LATENT"]), int(consts["HODE_FLOW_MAX_FLOWS"]), int(consts["HODE_FLOW_MAX_SAMPLES"])) == \
         (F.MAX_LATENT, F.MAX_FLOWS, F.MAX_SAMPLES)
 
 
 def test_struct_size_matches_the_c_header(tmp_path):
     from hode import _flow_lib as F
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include "%s"\nint main(){printf("%%zu %%zu %%zu\\n", sizeof(hode_flow_desc), '
-                   'offsetof(hode_flow_desc, mu), offsetof(hode_flow_desc, grad_b));return 0;}\n' % HEADER)
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", str(src), "-o", str(exe)])
-    size, off_mu, off_gb = (int(v) for v in subprocess.check_output([str(exe)]).split())
-    assert ctypes.sizeof(F.FlowDesc) == size and F.FlowDesc.mu.offset == off_mu and F.FlowDesc.grad_b.offset == off_gb
+    abi_checks.assert_c_layout("hode_flow.h", "hode_flow_desc", F.FlowDesc, tmp_path)
 
 
 def test_argument_errors_do_not_launch(flow_lib):
@@ -225,12 +213,12 @@ def test_argument_errors_do_not_launch(flow_lib):
 
 
 def test_library_digest_matches_sources():
-    import build_hip
-    stamp = build_hip.FLOW_OUT + ".digest"
-    if not os.path.exists(build_hip.FLOW_OUT):
-        build_hip.build(verbose=False)
-    assert os.path.exists(stamp), "libhode_flow.so has no source digest: rebuild with `python build_hip.py`"
-    assert open(stamp).read().strip() == build_hip.flow_source_digest(), "libhode_flow.so is stale: run `python build_hip.py`"
+    abi_checks.assert_digest_current("libhode_flow.so")
+
+
+def test_a_stale_library_is_refused_with_a_message(tmp_path, monkeypatch):
+    from hode import _flow_lib as F
+    abi_checks.assert_stale_library_is_refused(F.LIBRARY, tmp_path, monkeypatch)
 
 
 def test_every_flow_kernel_is_reached_by_a_gpu_case():

@@ -3,25 +3,23 @@ the reference's own numbers (G12, tests/golden/make_golden_ensemble.py) with the
 replaced by their oracles (test-only hooks), the residual and the ensemble flow of the two experiment scripts end to end
 on hode.batches folds, libhode_mix.so's C ABI, and the guards that every compiled mix kernel is reached by a case of the
 GPU test table and that no accepted shape asks for more LDS than a workgroup has."""
-import ctypes
 import glob
 import os
 import re
 import struct
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+import abi_checks
 import mix_cases as mc
 import model
 import training_utils
 from oracle.solvers import odeint as oracle_odeint
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hode_mix.h")
 MIX_SRC = os.path.join(ROOT, "hybrid-ode-neurips-2021_amd", "csrc", "mix", "hode_mix.hip")
 MIX_BUILD = os.path.join(ROOT, "hybrid-ode-neurips-2021_amd", "csrc", "mix", "build")
 CPU = torch.device("cpu")
@@ -247,16 +245,13 @@ def test_oracle_stand_in_is_the_reference_loop():
 @pytest.fixture(scope="module")
 def mix_lib():
     from hode import _mix_lib as M
-    if not os.path.exists(M.library_path()):
-        import build_hip
-        build_hip.build(verbose=False)
-    return M.lib()
+    return abi_checks.built(M.LIBRARY)
 
 
 def test_header_functions_are_exported_and_bound(mix_lib):
     from hode import _mix_lib as M
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = set(re.findall(r"\b(hode_mix_[a-z0-9_]+)\s*\(", src))
+    src = abi_checks.header_text("hode_mix.h")
+    declared = abi_checks.declared_functions("hode_mix.h", "hode_mix_")
     assert declared == {name for name, _, _ in M.EXPORTS} == {"hode_mix_version", "hode_mix_last_error_string", "hode_mix_crps"}
     for name in declared:
         assert getattr(mix_lib, name) is not None
@@ -269,15 +264,7 @@ def test_header_functions_are_exported_and_bound(mix_lib):
 
 def test_struct_size_matches_the_c_header(tmp_path):
     from hode import _mix_lib as M
-    fields = [n for n, _ in M.MixCrpsDesc._fields_]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include "%s"\nint main(){printf("%%zu", sizeof(hode_mix_crps_desc));\n%s\nreturn 0;}\n'
-                   % (HEADER, "\n".join('printf(" %%zu", offsetof(hode_mix_crps_desc, %s));' % f for f in fields)))
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", str(src), "-o", str(exe)])
-    nums = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert ctypes.sizeof(M.MixCrpsDesc) == nums[0]
-    assert [getattr(M.MixCrpsDesc, f).offset for f in fields] == nums[1:]
+    abi_checks.assert_c_layout("hode_mix.h", "hode_mix_crps_desc", M.MixCrpsDesc, tmp_path)
 
 
 def _shape_desc(obs=20, M_=50, De=4, Dm=6):
@@ -314,30 +301,12 @@ def test_argument_errors_do_not_launch(mix_lib):
 
 
 def test_library_digest_matches_sources():
-    import build_hip
-    stamp = build_hip.MIX_OUT + ".digest"
-    if not os.path.exists(build_hip.MIX_OUT):
-        build_hip.build(verbose=False)
-    assert os.path.exists(stamp), "libhode_mix.so has no source digest: rebuild with `python build_hip.py`"
-    assert open(stamp).read().strip() == build_hip.mix_source_digest(), "libhode_mix.so is stale: run `python build_hip.py`"
+    abi_checks.assert_digest_current("libhode_mix.so")
 
 
 def test_a_stale_library_is_refused_with_a_message(tmp_path, monkeypatch):
-    import shutil
-    import build_hip
-    from hode import HodeConfigError, _mix_lib as M
-    if not os.path.exists(build_hip.MIX_OUT):
-        build_hip.build(verbose=False)
-    monkeypatch.setattr(M, "_lib", None)
-    monkeypatch.setattr(M, "_HERE", str(tmp_path))
-    with pytest.raises(HodeConfigError, match="not found"):
-        M.lib()
-    shutil.copy(build_hip.MIX_OUT, tmp_path / "libhode_mix.so")
-    (tmp_path / "libhode_mix.so.digest").write_text("0" * 64 + "\n")
-    with pytest.raises(HodeConfigError, match="stale"):
-        M.lib()
-    shutil.copy(build_hip.MIX_OUT + ".digest", tmp_path / "libhode_mix.so.digest")
-    assert M.lib().hode_mix_version() == M.HODE_MIX_ABI_VERSION
+    from hode import _mix_lib as M
+    abi_checks.assert_stale_library_is_refused(M.LIBRARY, tmp_path, monkeypatch)
 
 
 # --------------------------------------------------------------------------------------------- kernel accounting

@@ -1,0 +1,42 @@
+"""Is the device code of two built trees the same?  python tools/device_code_diff.py <tree A> <tree B>
+
+For every object under csrc/**/build/ of both trees (experiment objects `<unit>__<tag>.o` aside): the .text bytes of its
+gfx950 code object and every kernel descriptor.  Prints one row per unit and exits 1 on any difference.  Symbol names are
+not compared (the compilation-unit id in them follows the source path)."""
+import glob, hashlib, os, subprocess, sys, tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_descriptor import B, code_object, kernel_descriptors
+
+CSRC = os.path.join("hybrid-ode-neurips-2021_amd", "csrc")
+
+
+def objects(tree):
+    found = glob.glob(os.path.join(tree, CSRC, "build", "*.o")) + glob.glob(os.path.join(tree, CSRC, "*", "build", "*.o"))
+    return {os.path.relpath(o, os.path.join(tree, CSRC)): o for o in found if "__" not in os.path.basename(o)}
+
+
+def text_bytes(obj):
+    """The .text section of the object's gfx950 code object; None for a host-only unit."""
+    with tempfile.TemporaryDirectory(prefix="hode_dcd_") as tmp:
+        co = code_object(obj, tmp)
+        if co is None:
+            return None
+        text = os.path.join(tmp, "text.bin")
+        subprocess.run([B + "llvm-objcopy", "--dump-section", ".text=" + text, co, os.path.join(tmp, "dummy.co")], check=True)
+        return open(text, "rb").read()
+
+
+if __name__ == "__main__":
+    a, b = objects(sys.argv[1]), objects(sys.argv[2])
+    bad = sorted(set(a) ^ set(b))
+    print("%-28s %10s %8s  %-12s %s" % ("unit", ".text B", "kernels", ".text sha256", "result"))
+    for unit in sorted(set(a) & set(b)):
+        ta, tb = text_bytes(a[unit]), text_bytes(b[unit])
+        ka, kb = sorted(kernel_descriptors(a[unit])), sorted(kernel_descriptors(b[unit]))
+        same = ta == tb and ka == kb
+        bad += [] if same else [unit]
+        print("%-28s %10d %8d  %-12s %s" % (unit, len(ta or b""), len(ka), hashlib.sha256(ta or b"").hexdigest()[:12],
+                                            "identical" if same else "DIFFERENT (text %s, descriptors %s)" % (ta == tb, ka == kb)))
+    print("%d units compared; %s" % (len(set(a) & set(b)), "all identical" if not bad else "DIFFERENT or unmatched: %s" % bad))
+    sys.exit(1 if bad else 0)

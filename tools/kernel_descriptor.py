@@ -7,17 +7,25 @@ import os, re, struct, subprocess, sys, tempfile
 B = "/opt/rocm/lib/llvm/bin/"
 
 
+def code_object(obj, tmp):
+    """Path of the object's gfx950 code object, extracted into directory `tmp`; None for a host-only unit."""
+    fb, co = os.path.join(tmp, "fb.bin"), os.path.join(tmp, "k.co")
+    r = subprocess.run([B + "llvm-objcopy", "--dump-section", ".hip_fatbin=" + fb, obj, os.path.join(tmp, "fb_dummy.o")],
+                       capture_output=True, text=True)
+    if r.returncode != 0:
+        if "not found" in r.stderr:
+            return None  # no device code
+        raise RuntimeError("llvm-objcopy %s: %s" % (obj, r.stderr))
+    subprocess.run([B + "clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fb,
+                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
+    return co
+
+
 def kernel_descriptors(obj):
     with tempfile.TemporaryDirectory(prefix="hode_kd_") as tmp:
-        fb, co = os.path.join(tmp, "fb.bin"), os.path.join(tmp, "k.co")
-        r = subprocess.run([B + "llvm-objcopy", "--dump-section", ".hip_fatbin=" + fb, obj, os.path.join(tmp, "fb_dummy.o")],
-                           capture_output=True, text=True)
-        if r.returncode != 0:
-            if "not found" in r.stderr:
-                return []  # a host-only unit: no device code
-            raise RuntimeError("llvm-objcopy %s: %s" % (obj, r.stderr))
-        subprocess.run([B + "clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fb,
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
+        co = code_object(obj, tmp)
+        if co is None:
+            return []
         sec = subprocess.run([B + "llvm-readelf", "-S", co], capture_output=True, text=True, check=True).stdout
         syms = subprocess.run([B + "llvm-readelf", "-s", "-W", co], capture_output=True, text=True, check=True).stdout
         data = open(co, "rb").read()
