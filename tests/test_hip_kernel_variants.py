@@ -82,7 +82,8 @@ def test_seqdec(case):
 
 
 # ------------------------------------------------------------------------------------------------------- neural-real
-def _neural_real(kind, D, method, H, B, perturb, div, dev, t0=3, t_end=9, Ta=7, seed=0):
+def _neural_real(kind, D, method, H, B, perturb, div, dev, t0=3, t_end=9, Ta=7, seed=0, t=None):
+    """`t`: the output grid (default arange(t0 - 1, t_end)); div = None solves on the grid itself (no step_size option)."""
     import hode
     import model
     gen = torch.Generator().manual_seed(seed)
@@ -91,18 +92,19 @@ def _neural_real(kind, D, method, H, B, perturb, div, dev, t0=3, t_end=9, Ta=7, 
     ode = cls(D, ACT, STAT, H, t_end, 1, device=dev)
     y0 = torch.randn(B, D, generator=gen) * 0.5
     a = (torch.rand(Ta, B, 1, generator=gen) < 0.4).float() * torch.rand(Ta, B, 1, generator=gen) * 2
-    t = torch.arange(t0 - 1, t_end, 1.0)
+    t = torch.arange(t0 - 1, t_end, 1.0) if t is None else t
+    step = None if div is None else 1.0 / div
     cot = torch.randn(t.numel(), B, D, generator=gen)
     ode.set_action_static(a.to(dev), None)
     yg = y0.to(dev).requires_grad_(True)
-    h = hode.odeint(ode, yg, t.to(dev), method=method, options={"step_size": 1.0 / div, "perturb": perturb})
+    h = hode.odeint(ode, yg, t.to(dev), method=method, options=dict({"perturb": perturb}, **({} if step is None else {"step_size": step})))
     (h * cot.to(dev)).sum().backward()
     got = [yg.grad] + [p.grad for p in ode.ml_net.parameters()]
     ps = [p.detach().cpu().double().requires_grad_(True) for p in ode.ml_net.parameters()]
     yc = y0.double().requires_grad_(True)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        hc, _ = neural_real_eager.solve(kind, yc, *ps, a.double(), t.double(), method, step_size=1.0 / div, perturb=perturb)
+        hc, _ = neural_real_eager.solve(kind, yc, *ps, a.double(), t.double(), method, step_size=step, perturb=perturb)
     (hc * cot.double()).sum().backward()
     return h, hc, got, [yc.grad] + [p.grad for p in ps]
 
@@ -154,21 +156,23 @@ def _real_flat(f):
 
 
 @functools.lru_cache(maxsize=None)
-def _real_problem(D, H, method, perturb=True, B=37, Ta=12, t0=4):
-    """Inputs and the fp64 oracle (h, grad_y0, flat weight gradient, theta gradient) of sum(h * cot)."""
+def _real_problem(D, H, method, perturb=True, B=37, Ta=12, t0=4, t=None):
+    """Inputs and the fp64 oracle (h, grad_y0, flat weight gradient, theta gradient) of sum(h * cot).  `t`: the grid as a
+    tuple (default arange(t0 - 1, Ta), solved with step_size 1); a given grid is the solver grid itself."""
     from oracle.rhs import RocheRealRHS
     from oracle.solvers import odeint as oracle_odeint
     gen = torch.Generator().manual_seed(D + H)
     torch.manual_seed(D + 3 * H)
     f = RocheRealRHS(D, H)
     a = (torch.rand(Ta, B, 1, generator=gen) < 0.2).float() * torch.rand(Ta, B, 1, generator=gen)
-    t = torch.arange(t0 - 1, Ta, 1, dtype=torch.float32)
+    opts = {"perturb": perturb} if t is not None else {"perturb": perturb, "step_size": 1.0}
+    t = torch.arange(t0 - 1, Ta, 1, dtype=torch.float32) if t is None else torch.tensor(t, dtype=torch.float32)
     y0 = torch.randn(B, D, generator=gen) * 0.3
     cot = torch.randn(t.numel(), B, D, generator=gen)
     f64 = copy.deepcopy(f).double()
     f64.set_action_static(a.double())
     y64 = y0.double().requires_grad_(True)
-    ho = oracle_odeint(f64, y64, t.double(), method=method, options={"perturb": perturb, "step_size": 1.0})
+    ho = oracle_odeint(f64, y64, t.double(), method=method, options=opts)
     (ho * cot.double()).sum().backward()
     ref = dict(h=ho.detach(), gy0=y64.grad, gw=torch.cat([p.grad.reshape(-1) for p in _real_flat(f64)]),
                gth=torch.stack([f64.k_immunity.grad, f64.kel.grad, f64.kel2.grad]))
@@ -240,10 +244,13 @@ def _theta_names(ablate):
     return list(THETA_NAMES) + (["theta_1", "theta_2"] if ablate else [])
 
 
-def _roche_setup(D, ablate, N, T, seed, theta=kv.THETA_DEFAULT, n_dose=1, neg_imm=False):
+def _roche_setup(D, ablate, N, T, seed, theta=kv.THETA_DEFAULT, n_dose=1, neg_imm=False, t=None):
     from hode import synth
     from oracle.rhs import RocheRHS
     inp = synth.solver_inputs(N, T, D, seed=seed, n_dose=n_dose)
+    if t is not None:  # another output grid than synth.grid(T)
+        assert t.numel() == T
+        inp["t"] = t
     if n_dose > 1:  # Dose(t) sums K decays of the patient's largest dose: keep it at one dose's scale, or the -Dose2 * ir
         inp["actions"] /= n_dose  # term drives ir below zero inside a stage and ir ** HillPatho's log (grad theta) is NaN
     if neg_imm:  # every other patient starts with a negative Immunity (the base of imm ** HillCure)
@@ -290,7 +297,7 @@ def _roche_problem(D, method, ablate, key=("default", None, 1, False)):
     return dict(y0=inp["z0"], t=inp["t"], dosage=dosage, times=times, theta=theta, w=w, b=b, cot=cot), ref
 
 
-def _roche_plan(p, dev, method, ablate, lanes, need_theta, tape):
+def _roche_plan(p, dev, method, ablate, lanes, need_theta, tape, perturb=False):
     from hode import _lib as L
     from hode.plan import RocheRKPlan
     theta = torch.zeros(L.N_THETA)
@@ -298,7 +305,7 @@ def _roche_plan(p, dev, method, ablate, lanes, need_theta, tape):
     opt = lambda x: None if x is None else x.to(dev)  # noqa: E731
     plan = RocheRKPlan(p["y0"].to(dev), theta.to(dev), opt(p["w"]), opt(p["b"]), p["t"].to(dev), p["dosage"].to(dev),
                        p["times"].to(dev), method=method, ablate=ablate, lanes_per_patient=lanes,
-                       need_theta_grad=need_theta, tape=tape)
+                       need_theta_grad=need_theta, tape=tape, perturb=perturb)
     plan.grad_h.copy_(p["cot"])
     plan.forward()
     gy0, _ = plan.backward()
