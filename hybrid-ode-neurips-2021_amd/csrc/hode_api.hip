@@ -48,10 +48,6 @@ __global__ __launch_bounds__(64) void fold_partials_kernel(const float* __restri
 // patients per wave: as many waves as it takes to put one on (almost) every SIMD, then whole rounds of 1024
 int patients_per_wave(int B, int lpp) {
   const int cap = 64 / lpp;
-  if (const char* env = getenv("HODE_PPW")) {  // tuning / test override
-    const int v = atoi(env);
-    if (v >= 1 && v <= cap) return v;
-  }
   const long long simds = 1024;
   const long long rounds = (B + simds * cap - 1) / (simds * cap);
   long long ppw = (B + simds * rounds - 1) / (simds * rounds);
@@ -109,26 +105,24 @@ RkArgs make_args(const hode_solve_desc* d) {
   return a;
 }
 
-// lanes_per_patient == 16 (or HODE_RK_LAYOUT=m) selects the MFMA layout (hode_rk_mf.hip) where it exists for the dimension
+// lanes_per_patient == 16 selects the MFMA layout (hode_rk_mf.hip) where it exists for the dimension
 bool use_mf(const hode_solve_desc* d) {
   if (!hode::mf_supported(d)) return false;
   if (d->lanes_per_patient == 16) return true;
   if (d->lanes_per_patient != 0) return false;
-  if (const char* env = getenv("HODE_RK_LAYOUT")) return env[0] == 'm';
   // measured at 10 000 patients (T=100, D=12, rk4): MFMA layout fwd 118 us / bwd 313 us vs quad layout 104 / 339 -- a
   // wash (the 3 dependent 16x16x4 MFMAs + hazard nops cost as much latency as the 24 fmas they replace), so the quad
   // layout stays the default and the MFMA layout is opt-in
   return false;
 }
 
-// lanes_per_patient == 48 / HODE_RK_LAYOUT=s select the wave-specialised split layout (hode_rk_split.hip); it is also the
-// default for the dimensions it is built for (HODE_RK_LAYOUT=q forces the quad layout)
+// lanes_per_patient == 48 selects the wave-specialised split layout (hode_rk_split.hip); it is also the default for the
+// dimensions it is built for (lanes_per_patient == 4 forces the quad layout)
 bool use_split(const hode_solve_desc* d, bool bwd) {
   if (!hode::split_supported(d)) return false;
   if (bwd && d->n_times < 2) return false;
   if (d->lanes_per_patient == 48) return true;
   if (d->lanes_per_patient != 0) return false;
-  if (const char* env = getenv("HODE_RK_LAYOUT")) return env[0] == 's';
   // default wherever it exists: measured at 10 000 patients (T=100, D=12, rk4) fwd 70 us / bwd 161 us vs 104 / 339 us
   // for the quad layout; it also issues fewer wave-instructions per patient (4.1 vs 7.3 per rhs), so it keeps winning
   // once every SIMD is busy

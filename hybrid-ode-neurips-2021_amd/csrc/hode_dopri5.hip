@@ -36,12 +36,8 @@ static_assert(sizeof(hode::DpInit) == sizeof(hode_dopri5_init_record), "DpInit i
 // SIMD (hode::patients_per_wave) because they stream h every step; an attempt launch has no such stream, its cost per
 // wave does not depend on the number of live lanes, and every extra wave is one more workgroup to dispatch and one more
 // error-norm partial for every wave of the next launch to read: 6.0-6.1 us per attempt with 16 patients per wave against
-// 6.3 with 10 at 10 000 patients (A/B, same call); the backward is indifferent.  HODE_PPW still overrides.
-int dp_patients_per_wave(const hode_solve_desc* d) {
-  const int cap = 64 / hode::choose_lpp(d);
-  if (getenv("HODE_PPW")) return hode::patients_per_wave(d->batch, hode::choose_lpp(d));
-  return cap;
-}
+// 6.3 with 10 at 10 000 patients (A/B, same call); the backward is indifferent.
+int dp_patients_per_wave(const hode_solve_desc* d) { return 64 / hode::choose_lpp(d); }
 int dp_n_waves(const hode_solve_desc* d) {
   const int ppw = dp_patients_per_wave(d);
   return (d->batch + ppw - 1) / ppw;

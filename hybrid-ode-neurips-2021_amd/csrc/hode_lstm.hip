@@ -93,10 +93,8 @@ int lstm_geom(const hode_lstm_desc* d, LstmGeom* G, bool bwd_compatible) {
   G->fNW = G->TPW <= 5 ? 4 : 8;
   G->fTPW = G->TPW * 4 / G->fNW;
   G->NT = choose_nt(d->batch, bwd_compatible);
-  if (const char* env = getenv("HODE_LSTM_NT")) {  // tuning / test override of the patient tile (16 * NT)
-    const int v = atoi(env);
-    if (v >= 1 && v <= (bwd_compatible ? 3 : 4)) G->NT = v;
-  }
+  // tuning / test override of the patient tile (16 * NT)
+  if (d->patient_tiles >= 1 && d->patient_tiles <= (bwd_compatible ? 3 : 4)) G->NT = d->patient_tiles;
   G->BT = 16 * G->NT;
   G->nblk = (d->batch + G->BT - 1) / G->BT;
   G->Kq = (d->input_dim + Hp + 1 + 3) / 4;   // + the ones row that carries the bias

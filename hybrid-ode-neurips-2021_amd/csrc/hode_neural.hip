@@ -268,12 +268,12 @@ struct NeuralLayout {
   size_t w2t, a1t, u1t, yet, u2t, total;
 };
 
+// default (lanes_per_patient 0 or 16): the matrix-core kernels (hode_neural_mf.hip); 1 selects the one-patient-per-lane ones
+bool neural_lanes(const hode_solve_desc* d) { return d->lanes_per_patient == 1; }
+
 // the matrix-core backward accumulates the weight gradients on chip when the caller hands it the accumulators (grad_w1 set);
-// HODE_NEURAL_LAYOUT=t (lane-per-patient kernels) and callers without accumulators get the operand tapes
-bool neural_onchip(const hode_solve_desc* d) {
-  const char* env = getenv("HODE_NEURAL_LAYOUT");
-  return !(env && env[0] == 't') && d->grad_w1 != nullptr;
-}
+// the lane-per-patient kernels and callers without accumulators get the operand tapes
+bool neural_onchip(const hode_solve_desc* d) { return !neural_lanes(d) && d->grad_w1 != nullptr; }
 
 NeuralLayout neural_layout(const hode_solve_desc* d, bool bwd) {
   const size_t D = d->latent_dim, HD = 10 * D, B = d->batch;
@@ -298,6 +298,8 @@ NeuralLayout neural_layout(const hode_solve_desc* d, bool bwd) {
 int check_neural(const hode_solve_desc* d, bool bwd) {
   if (d->method < HODE_METHOD_EULER || d->method > HODE_METHOD_RK4_38)
     return hode::fail(HODE_E_UNSUPPORTED, "neural rhs: unknown fixed-grid method %d", d->method);
+  if (d->lanes_per_patient != 0 && d->lanes_per_patient != 1 && d->lanes_per_patient != 16)
+    return hode::fail(HODE_E_UNSUPPORTED, "neural rhs: lanes_per_patient %d (have 0 = library chooses, 1, 16)", d->lanes_per_patient);
   if (d->batch <= 0 || d->n_times <= 0 || d->n_dose < 0) return hode::fail(HODE_E_SIZE, "bad sizes");
   if (d->latent_dim < 4 || d->latent_dim > 14 || (d->latent_dim & 1))
     return hode::fail(HODE_E_UNSUPPORTED, "neural rhs: latent_dim %d has no compiled kernel (have 4, 6, 8, 10, 12, 14)", d->latent_dim);
@@ -351,14 +353,10 @@ int neural_rk(const hode_solve_desc* d, bool bwd, hipStream_t s) {
   a.a1t = (float*)(ws + L.a1t); a.u1t = (float*)(ws + L.u1t); a.yet = (float*)(ws + L.yet); a.u2t = (float*)(ws + L.u2t);
   a.B = d->batch; a.T = d->n_times; a.K = d->n_dose; a.perturb = d->perturb;
   a.w2 = d->w2;
-  {
-    // default: the matrix-core kernels (hode_neural_mf.hip); HODE_NEURAL_LAYOUT=t selects the one-patient-per-lane ones
-    const char* env = getenv("HODE_NEURAL_LAYOUT");
-    if (!(env && env[0] == 't')) return launch_neural_mf(d, a, bwd, s);
-  }
+  if (!neural_lanes(d)) return launch_neural_mf(d, a, bwd, s);
   const int D = d->latent_dim, HD = 10 * D;
   if (D != 6 && D != 8 && D != 12)
-    return hode::fail(HODE_E_UNSUPPORTED, "neural rhs: the lane-per-patient layout (HODE_NEURAL_LAYOUT=t) is compiled for 6, 8, 12 only");
+    return hode::fail(HODE_E_UNSUPPORTED, "neural rhs: the lane-per-patient layout (lanes_per_patient = 1) is compiled for 6, 8, 12 only");
   hipLaunchKernelGGL(hode::transpose_w2_kernel, dim3((D * HD + 255) / 256), dim3(256), 0, s, d->w2, (float*)(ws + L.w2t), D, HD);
   if (int e = hode::hip_fail(hipGetLastError(), "transpose_w2 launch")) return e;
   switch (D) {

@@ -288,14 +288,14 @@ __global__ __launch_bounds__(64) void readout_fold_kernel(const float* __restric
 namespace {
 constexpr int kReadoutWaves = 2048;  // grid-stride: two waves per SIMD keep enough loads in flight for an HBM-bound pass
 
-// matrix-core kernel: the two shipped shapes
-bool readout_mf(int latent, int obs) {
-  if (getenv("HODE_READOUT_VALU")) return false;   // A/B switch for the lane-per-4-outputs kernel
+// matrix-core kernel: the two shipped shapes, unless the caller asks for the lane-per-4-outputs kernel
+bool readout_mf(int latent, int obs, int variant) {
+  if (variant == HODE_READOUT_VARIANT_VALU) return false;
   return (latent == 12 && obs > 48 && obs <= 80) || (latent == 8 && obs > 32 && obs <= 48);
 }
 
-int readout_waves(long long rows, int obs, int latent) {
-  const int rpi = readout_mf(latent, obs) ? 16 : 64 / (obs / 4);
+int readout_waves(long long rows, int obs, int latent, int variant) {
+  const int rpi = readout_mf(latent, obs, variant) ? 16 : 64 / (obs / 4);
   const long long iters = (rows + rpi - 1) / rpi;
   return (int)(iters < kReadoutWaves ? (iters > 0 ? iters : 1) : kReadoutWaves);
 }
@@ -304,7 +304,7 @@ int readout_waves(long long rows, int obs, int latent) {
 extern "C" size_t hode_readout_workspace_bytes(const hode_readout_desc* d) {
   if (!d || d->struct_size != sizeof(hode_readout_desc) || d->obs_dim <= 0 || d->obs_dim % 4 || d->obs_dim > 128) return 0;
   const size_t P = 1 + (size_t)d->obs_dim * d->latent_dim + d->obs_dim;
-  return (size_t)readout_waves(d->rows, d->obs_dim, d->latent_dim) * P * sizeof(float);
+  return (size_t)readout_waves(d->rows, d->obs_dim, d->latent_dim, d->variant) * P * sizeof(float);
 }
 
 extern "C" int hode_readout_sse(const hode_readout_desc* d, void* stream) {
@@ -315,6 +315,8 @@ extern "C" int hode_readout_sse(const hode_readout_desc* d, void* stream) {
     return hode::fail(HODE_E_UNSUPPORTED, "readout: obs_dim %d must be a multiple of 4 and <= 128", d->obs_dim);
   if (d->latent_dim != 4 && d->latent_dim != 6 && d->latent_dim != 8 && d->latent_dim != 12)
     return hode::fail(HODE_E_UNSUPPORTED, "readout: latent_dim %d has no compiled kernel (have 4, 6, 8, 12)", d->latent_dim);
+  if (d->variant != 0 && d->variant != HODE_READOUT_VARIANT_VALU)
+    return hode::fail(HODE_E_UNSUPPORTED, "readout: variant %d (have 0 = library chooses, HODE_READOUT_VARIANT_VALU)", d->variant);
   if (!d->h || !d->x || !d->mask || !d->w || !d->b || !d->lik) return hode::fail(HODE_E_NULL, "h / x / mask / w / b / lik must be non-NULL");
   if (((uintptr_t)d->x | (uintptr_t)d->mask | (uintptr_t)d->h) & 15) return hode::fail(HODE_E_ALIGN, "h / x / mask must be 16-byte aligned");
   const size_t need = hode_readout_workspace_bytes(d);
@@ -323,9 +325,9 @@ extern "C" int hode_readout_sse(const hode_readout_desc* d, void* stream) {
   hode::ReadoutArgs a{};
   a.h = d->h; a.x = d->x; a.mask = d->mask; a.wo = d->w; a.bo = d->b; a.grad_h = d->grad_h; a.partials = (float*)d->workspace;
   a.R = d->rows; a.OBS = d->obs_dim; a.scale = d->scale;
-  const int nw = readout_waves(d->rows, d->obs_dim, d->latent_dim);
+  const int nw = readout_waves(d->rows, d->obs_dim, d->latent_dim, d->variant);
   hipStream_t s = (hipStream_t)stream;
-  if (readout_mf(d->latent_dim, d->obs_dim)) {
+  if (readout_mf(d->latent_dim, d->obs_dim, d->variant)) {
     if (d->latent_dim == 12) {
       if (grad) hipLaunchKernelGGL((hode::readout_mf_kernel<12, 5, true>), dim3(nw), dim3(64), 0, s, a);
       else hipLaunchKernelGGL((hode::readout_mf_kernel<12, 5, false>), dim3(nw), dim3(64), 0, s, a);

@@ -334,11 +334,12 @@ struct RealLayout {
   size_t tape, partials, dose, total;
 };
 // [ tape (bwd) | theta partials (bwd) | dose table (both) ]; the tape stays first: hode/real.py views it from offset 0
+// default where it exists (D = 20, hidden <= 64; lanes_per_patient 0 or 16): the matrix-core kernels of hode_real_mf.hip,
+// 16 patients per wave; lanes_per_patient == 1 forces the one-patient-per-lane kernels of this file
+bool real_mf(const hode_solve_desc* d) { return hode::real_mf_supported(d) && d->lanes_per_patient != 1; }
+
 // the matrix-core backward accumulates the weight gradients on chip when the caller hands it the flat accumulator (grad_w1)
-bool real_onchip(const hode_solve_desc* d) {
-  const char* env = getenv("HODE_REAL_LAYOUT");
-  return hode::real_mf_supported(d) && !(env && env[0] == 't') && d->grad_w1 != nullptr;
-}
+bool real_onchip(const hode_solve_desc* d) { return real_mf(d) && d->grad_w1 != nullptr; }
 
 RealLayout real_layout(const hode_solve_desc* d, bool bwd) {
   RealLayout L{0, 0, 0, 0};
@@ -357,6 +358,8 @@ RealLayout real_layout(const hode_solve_desc* d, bool bwd) {
 int check_real(const hode_solve_desc* d, bool bwd) {
   if (d->method < HODE_METHOD_EULER || d->method > HODE_METHOD_RK4_38)
     return hode::fail(HODE_E_UNSUPPORTED, "real rhs: unknown fixed-grid method %d", d->method);
+  if (d->lanes_per_patient != 0 && d->lanes_per_patient != 1 && d->lanes_per_patient != 16)
+    return hode::fail(HODE_E_UNSUPPORTED, "real rhs: lanes_per_patient %d (have 0 = library chooses, 1, 16)", d->lanes_per_patient);
   if (d->batch <= 0 || d->n_times <= 0 || d->hidden_dim <= 0 || d->n_action_times <= 0)
     return hode::fail(HODE_E_SIZE, "bad sizes: batch=%d n_times=%d hidden=%d n_action_times=%d", d->batch, d->n_times,
                       d->hidden_dim, d->n_action_times);
@@ -399,10 +402,7 @@ int real_rk(const hode_solve_desc* d, bool bwd, hipStream_t s) {
   a.partials = bwd ? (float*)(ws + L.partials) : nullptr;
   a.dose_tab = (float*)(ws + L.dose);
   a.B = d->batch; a.T = d->n_times; a.Ta = d->n_action_times; a.H = d->hidden_dim; a.perturb = d->perturb;
-  // default where it exists (D = 20, hidden <= 64): the matrix-core kernels of hode_real_mf.hip, 16 patients per wave;
-  // HODE_REAL_LAYOUT=t forces the one-patient-per-lane kernels of this file
-  const char* env = getenv("HODE_REAL_LAYOUT");
-  const bool mf = real_mf_supported(d) && !(env && env[0] == 't');
+  const bool mf = real_mf(d);
   int e;
   if (mf) e = launch_real_mf(d, a, bwd, s);
   else if (d->latent_dim == 4) e = bwd ? launch_real<4, true>(d, a, s) : launch_real<4, false>(d, a, s);

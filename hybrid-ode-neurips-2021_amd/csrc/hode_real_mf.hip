@@ -1,7 +1,7 @@
 // Real-data hybrid rhs (two small MLPs + GRU-ODE block, reference model.py:613-645) on the matrix cores, inside the
 // fixed-grid euler / midpoint / rk4(3/8) loop and its discrete adjoint, gfx950.  Same C-ABI contract, tape rows and
 // arithmetic (up to summation order) as the one-patient-per-lane kernels of hode_real.hip, which stay as the fallback
-// (HODE_REAL_LAYOUT=t, and for shapes outside D = 20, hidden <= 64).
+// (lanes_per_patient = 1, and for shapes outside D = 20, hidden <= 64).
 //
 // Recipe of hode_neural_mf.hip: a wave owns 16 patients for the whole time loop; with v_mfma_f32_16x16x4_f32 a vector over
 // <= 16 rows is one accumulator tile (lane (g, n): rows 4g + r of patient n in register r), every contraction is ordered

@@ -6,7 +6,7 @@ import ctypes as C
 
 from ._loader import HodeConfigError, Library  # noqa: F401
 
-HODE_ABI_VERSION = 1
+HODE_ABI_VERSION = 2
 
 RHS_ROCHE, RHS_ROCHE_ABLATE, RHS_NEURAL, RHS_ROCHE_REAL = 0, 1, 2, 3
 RHS_NEURAL_REAL, RHS_NEURAL_REAL_2ND = 4, 5
@@ -16,6 +16,7 @@ N_THETA = 16
 STATUS_NONFINITE, STATUS_DT_UNDERFLOW, STATUS_MAX_STEPS = 1, 2, 4
 WS_RK_FWD, WS_RK_BWD, WS_DOPRI5_FWD, WS_DOPRI5_BWD = 0, 1, 2, 3
 FLAG_SKIP_FOLD, FLAG_OVERWRITE_GRADS, FLAG_TAPE, FLAG_DETACH_FIRST_STEP, FLAG_NO_TAPE = 1, 2, 4, 8, 16
+READOUT_VARIANT_VALU = 1
 
 
 class HodeError(RuntimeError):
@@ -61,7 +62,7 @@ class LstmDesc(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("seq_len", C.c_int32), ("batch", C.c_int32), ("input_dim", C.c_int32), ("hidden_dim", C.c_int32),
-        ("obs_dim", C.c_int32), ("reverse", C.c_int32), ("save_tape", C.c_int32),
+        ("obs_dim", C.c_int32), ("reverse", C.c_int32), ("save_tape", C.c_int32), ("patient_tiles", C.c_int32),
         ("x", _fp), ("a", _fp), ("mask", _fp), ("w_ih", _fp), ("w_hh", _fp), ("b_ih", _fp), ("b_hh", _fp),
         ("h_out", _fp), ("c_out", _fp), ("grad_h_out", _fp), ("grad_gates", _fp), ("h_prev", _fp),
         ("workspace", _fp), ("workspace_bytes", C.c_size_t),
@@ -71,7 +72,7 @@ class LstmDesc(C.Structure):
 class ReadoutDesc(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("latent_dim", C.c_int32), ("obs_dim", C.c_int32), ("scale", C.c_float),
-        ("rows", C.c_int64),
+        ("variant", C.c_int32), ("rows", C.c_int64),
         ("h", _fp), ("x", _fp), ("mask", _fp), ("w", _fp), ("b", _fp), ("lik", _fp),
         ("grad_h", _fp), ("grad_w", _fp), ("grad_b", _fp),
         ("workspace", _fp), ("workspace_bytes", C.c_size_t),

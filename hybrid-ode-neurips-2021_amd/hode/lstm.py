@@ -6,8 +6,6 @@ the ``cat([x, a]) * cat([mask, 1])`` that feeds them.
 
 from __future__ import annotations
 
-import os
-
 import torch
 
 from . import _lib as L
@@ -48,10 +46,11 @@ def _desc(x, a, mask, w_ih, w_hh, b_ih, b_hh, reverse, save_tape):
     return d
 
 
-def lstm_final_state(x, a, mask, w_ih, w_hh, b_ih, b_hh, reverse=True):
+def lstm_final_state(x, a, mask, w_ih, w_hh, b_ih, b_hh, reverse=True, patient_tiles=0):
     """Forward only: final (h, c), each (B, H), after walking the window (reverse: t = T-1 .. 0).
 
-    x (T, B, obs), a (T, B, A) or None, mask (T, B, obs) or None; weights as ``nn.LSTM`` stores them.
+    x (T, B, obs), a (T, B, A) or None, mask (T, B, obs) or None; weights as ``nn.LSTM`` stores them.  ``patient_tiles``
+    forces the 16-patient tiles per workgroup (tuning / tests); 0 = the library chooses.
     """
     _require_gpu(x, w_ih)
     lib = L.lib()
@@ -61,7 +60,7 @@ def lstm_final_state(x, a, mask, w_ih, w_hh, b_ih, b_hh, reverse=True):
     h = torch.empty((B, H), device=x.device, dtype=torch.float32)
     c = torch.empty((B, H), device=x.device, dtype=torch.float32)
     d = _desc(xc, ac, mc, wi, wh, bi, bh, reverse, False)
-    d.h_out, d.c_out = h.data_ptr(), c.data_ptr()
+    d.patient_tiles, d.h_out, d.c_out = int(patient_tiles), h.data_ptr(), c.data_ptr()
     nbytes = lib.hode_lstm_workspace_bytes(d)
     if nbytes == 0:
         L.check(lib.hode_lstm_fwd(d, _stream()), "hode_lstm_fwd")  # reports why the shape is unsupported
@@ -96,10 +95,7 @@ def _splitk_tn(lhs, rhs):
         return lhs.t() @ rhs
     # The product is formed as (rhs^T lhs)^T: with M = 4H = 640 and N = 244 the library's 256 x 128 macro tile wastes 20 % on
     # the 640 x 244 result (3 x 2 tiles) and 5 % on 244 x 640 (1 x 5): 2.7 -> 2.3 ms at K = 1e6 in isolation
-    # (tools/gemm_orient_probe.py), 0.05 ms inside the training step (same-call A/B, HODE_LSTM_GEMM_MN=1)
-    if os.environ.get("HODE_LSTM_GEMM_MN"):   # A/B switch: the product in its natural orientation
-        part = torch.bmm(lhs.view(P, K // P, -1).transpose(1, 2), rhs.view(P, K // P, -1))
-        return (_ones_row(P, part) @ part.view(P, -1)).view(part.shape[1], part.shape[2])
+    # (tools/gemm_orient_probe.py), 0.05 ms inside the training step (same-call A/B)
     part = torch.bmm(rhs.view(P, K // P, -1).transpose(1, 2), lhs.view(P, K // P, -1))
     # fold the P partial products with a (1 x P) GEMM: torch's strided sum(0) over this shape reads at ~0.3 TB/s
     return (_ones_row(P, part) @ part.view(P, -1)).view(part.shape[1], part.shape[2]).t()
@@ -121,7 +117,7 @@ class _LstmEncode(torch.autograd.Function):
     Gradients for the four LSTM parameters; none for x, a, mask (their .grad stays None)."""
 
     @staticmethod
-    def forward(ctx, x, a, mask, w_ih, w_hh, b_ih, b_hh, reverse):
+    def forward(ctx, x, a, mask, w_ih, w_hh, b_ih, b_hh, reverse, patient_tiles):
         _require_gpu(x, w_ih)
         lib = L.lib()
         xc, ac, mc = _f32c(x), (None if a is None else _f32c(a)), (None if mask is None else _f32c(mask))
@@ -130,7 +126,7 @@ class _LstmEncode(torch.autograd.Function):
         h = torch.empty((B, H), device=x.device, dtype=torch.float32)
         c = torch.empty((B, H), device=x.device, dtype=torch.float32)
         d = _desc(xc, ac, mc, wi, wh, bi, bh, reverse, True)
-        d.h_out, d.c_out = h.data_ptr(), c.data_ptr()
+        d.patient_tiles, d.h_out, d.c_out = patient_tiles, h.data_ptr(), c.data_ptr()
         nbytes = lib.hode_lstm_workspace_bytes(d)
         if nbytes == 0:
             L.check(lib.hode_lstm_fwd(d, _stream()), "hode_lstm_fwd")
@@ -139,13 +135,13 @@ class _LstmEncode(torch.autograd.Function):
         with torch.cuda.device(x.device), _Span("lstm_fwd"):
             L.check(lib.hode_lstm_fwd(d, _stream()), "hode_lstm_fwd")
         ctx.save_for_backward(xc, ac if ac is not None else xc, mc if mc is not None else xc, wi, wh, bi, bh, ws)
-        ctx.flags = (ac is not None, mc is not None, bool(reverse))
+        ctx.flags = (ac is not None, mc is not None, bool(reverse), patient_tiles)
         return h
 
     @staticmethod
     def backward(ctx, grad_h):
         xc, ac, mc, wi, wh, bi, bh, ws = ctx.saved_tensors
-        has_a, has_m, reverse = ctx.flags
+        has_a, has_m, reverse, patient_tiles = ctx.flags
         ac = ac if has_a else None
         mc = mc if has_m else None
         lib = L.lib()
@@ -158,38 +154,31 @@ class _LstmEncode(torch.autograd.Function):
         W = (I + H + 1 + 3) // 4 * 4
         hprev = torch.empty((T, B, W), device=xc.device, dtype=torch.float32)  # [x*mask | a | h_prev | 1 | 0-pad]
         d = _desc(xc, ac, mc, wi, wh, bi, bh, reverse, True)
+        d.patient_tiles = patient_tiles
         h_dummy = torch.empty(1, device=xc.device)
         d.h_out, d.c_out = h_dummy.data_ptr(), h_dummy.data_ptr()  # unused by the backward, must be non-NULL
         d.grad_h_out, d.grad_gates, d.h_prev = gh.data_ptr(), dgates.data_ptr(), hprev.data_ptr()
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
         # The first obs columns of the operand rows (x * mask) do not depend on the recurrence: they are filled on a side stream
         # WHILE the BPTT kernel runs (it occupies 209 of the 256 CUs at the bench shape and is bound by the matrix pipe, the fill
-        # by HBM: off the critical path; HODE_LSTM_SERIAL_FILL=1 keeps it behind the kernel for A/Bs).
-        side = None if os.environ.get("HODE_LSTM_SERIAL_FILL") else _side_stream(xc.device)
-
-        def fill():   # the kernel leaves the first obs columns to the caller: x * mask, one streaming pass on the current stream
-            with torch.cuda.device(xc.device):
-                L.check(lib.hode_lstm_fill_operand(d, _stream()), "hode_lstm_fill_operand")
-
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())     # hprev's allocation and whatever produced x / mask
-            with torch.cuda.stream(side):
-                fill()
+        # by HBM: off the critical path).  The kernel leaves those columns to the caller: one streaming pass.
+        side = _side_stream(xc.device)
+        side.wait_stream(torch.cuda.current_stream())     # hprev's allocation and whatever produced x / mask
+        with torch.cuda.stream(side), torch.cuda.device(xc.device):
+            L.check(lib.hode_lstm_fill_operand(d, _stream()), "hode_lstm_fill_operand")
         with torch.cuda.device(xc.device), _Span("lstm_bwd"):
             L.check(lib.hode_lstm_bwd(d, _stream()), "hode_lstm_bwd")
         dg2 = dgates.view(T * B, 4 * H)
         with _Span("wgrad_gemm"):
-            if side is not None:
-                torch.cuda.current_stream().wait_stream(side)
-            else:
-                fill()
+            torch.cuda.current_stream().wait_stream(side)
             g = _splitk_tn(dg2, hprev.view(T * B, W))  # ONE product: [grad_w_ih | grad_w_hh | grad_b | 0]
         g_wih = g[:, :I].contiguous()
         g_whh = g[:, I:I + H].contiguous()
         g_b = g[:, I + H].contiguous()
-        return None, None, None, g_wih, g_whh, g_b, g_b.clone(), None
+        return None, None, None, g_wih, g_whh, g_b, g_b.clone(), None, None
 
 
-def lstm_encode(x, a, mask, w_ih, w_hh, b_ih, b_hh, reverse=True):
-    """Differentiable (w.r.t. the four LSTM parameters) final hidden state (B, H) of the masked window LSTM."""
-    return _LstmEncode.apply(x, a, mask, w_ih, w_hh, b_ih, b_hh, bool(reverse))
+def lstm_encode(x, a, mask, w_ih, w_hh, b_ih, b_hh, reverse=True, patient_tiles=0):
+    """Differentiable (w.r.t. the four LSTM parameters) final hidden state (B, H) of the masked window LSTM.
+    ``patient_tiles`` as in ``lstm_final_state``."""
+    return _LstmEncode.apply(x, a, mask, w_ih, w_hh, b_ih, b_hh, bool(reverse), int(patient_tiles))

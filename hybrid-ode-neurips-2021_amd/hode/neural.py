@@ -2,13 +2,12 @@
 
 The matrix-core backward kernel returns ``grad_y0`` and accumulates the weight gradients on chip (outer products over the
 wave's patients as MFMAs, one partial block per wave, fixed-order fold).  The one-patient-per-lane kernels
-(``HODE_NEURAL_LAYOUT=t``) tape the operands of those outer products instead and they are contracted here with batched
+(``lanes_per_patient=1``) tape the operands of those outer products instead and they are contracted here with batched
 BLAS GEMMs."""
 
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import torch
 
@@ -33,7 +32,7 @@ class _NeuralFixedGrid(torch.autograd.Function):
     """Gradients for y0 and the four weights; none for t, dosage, dose_times (their .grad stays None)."""
 
     @staticmethod
-    def forward(ctx, y0, w1, b1, w2, b2, t, dosage, dose_times, method, perturb):
+    def forward(ctx, y0, w1, b1, w2, b2, t, dosage, dose_times, method, perturb, lanes):
         _require_gpu(y0, w1, t, dosage, dose_times)
         lib = L.lib()
         y0c, tc, dosc, dtc = _f32c(y0), _f32c(t), _f32c(dosage), _f32c(dose_times)
@@ -41,26 +40,27 @@ class _NeuralFixedGrid(torch.autograd.Function):
         B, D = y0c.shape
         h = torch.empty((tc.numel(), B, D), device=y0.device, dtype=torch.float32)
         d = _desc(y0c, tc, dosc, dtc, w1c, b1c, w2c, b2c, h, method, perturb)
+        d.lanes_per_patient = lanes
         n = lib.hode_workspace_bytes(d, L.WS_RK_FWD)
         ws = torch.empty(max(n, 4), device=y0.device, dtype=torch.uint8)
         d.workspace, d.workspace_bytes = ws.data_ptr(), n
         with torch.cuda.device(y0.device):
             L.check(lib.hode_rk_fwd(d, _stream()), "hode_rk_fwd[neural]")
         ctx.save_for_backward(h, tc, dosc, dtc, w1c, b1c, w2c, b2c)
-        ctx.meta = (method, int(perturb))
+        ctx.meta = (method, int(perturb), lanes)
         return h
 
     @staticmethod
     def backward(ctx, grad_h):
         h, tc, dosc, dtc, w1c, b1c, w2c, b2c = ctx.saved_tensors
-        method, perturb = ctx.meta
+        method, perturb, lanes = ctx.meta
         lib = L.lib()
         T, B, D = h.shape
         gh = _f32c(grad_h)
         gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)
         d = _desc(h[0], tc, dosc, dtc, w1c, b1c, w2c, b2c, h, method, perturb)
-        d.grad_h, d.grad_y0 = gh.data_ptr(), gy0.data_ptr()
-        onchip = os.environ.get("HODE_NEURAL_LAYOUT", "")[:1] != "t"
+        d.lanes_per_patient, d.grad_h, d.grad_y0 = lanes, gh.data_ptr(), gy0.data_ptr()
+        onchip = lanes != 1
         if onchip:
             gw1, gb1, gw2, gb2 = (torch.zeros_like(x) for x in (w1c, b1c, w2c, b2c))
             d.grad_w1, d.grad_b1, d.grad_w2, d.grad_b2 = gw1.data_ptr(), gb1.data_ptr(), gw2.data_ptr(), gb2.data_ptr()
@@ -70,8 +70,8 @@ class _NeuralFixedGrid(torch.autograd.Function):
         with torch.cuda.device(h.device):
             L.check(lib.hode_rk_bwd(d, _stream()), "hode_rk_bwd[neural]")
         if onchip:
-            return gy0, gw1, gb1, gw2, gb2, None, None, None, None, None
-        return (gy0,) + contract_tape(ws, d, T, B, D, method) + (None, None, None, None, None)
+            return gy0, gw1, gb1, gw2, gb2, None, None, None, None, None, None
+        return (gy0,) + contract_tape(ws, d, T, B, D, method) + (None, None, None, None, None, None)
 
 
 def contract_tape(ws, d, T, B, D, method):
@@ -106,10 +106,12 @@ def contract_tape(ws, d, T, B, D, method):
     return gw1, gb1, gw2, gb2
 
 
-def neural_solve(y0, w1, b1, w2, b2, t, dosage, dose_times, method="rk4", perturb=False):
-    """h (T, B, D) for dy/dt = tanh(W2 tanh(W1 [y, Dose(t)] + b1) + b2); fixed-grid methods only."""
+def neural_solve(y0, w1, b1, w2, b2, t, dosage, dose_times, method="rk4", perturb=False, lanes_per_patient=0):
+    """h (T, B, D) for dy/dt = tanh(W2 tanh(W1 [y, Dose(t)] + b1) + b2); fixed-grid methods only.  ``lanes_per_patient``
+    forces a kernel family (tuning / tests): 1 = one patient per lane, 16 = matrix cores; 0 = the library chooses."""
     if method not in L.METHODS:
         raise L.HodeConfigError("hode: the neural rhs is built for the fixed-grid methods (euler, midpoint, rk4); got %r" % (method,))
     if dose_times.dim() != 2:
         dose_times = dose_times.reshape(y0.shape[0], -1)
-    return _NeuralFixedGrid.apply(y0, w1, b1, w2, b2, t, dosage, dose_times.to(torch.float32), L.METHODS[method], bool(perturb))
+    return _NeuralFixedGrid.apply(y0, w1, b1, w2, b2, t, dosage, dose_times.to(torch.float32), L.METHODS[method], bool(perturb),
+                                  int(lanes_per_patient))

@@ -19,7 +19,7 @@ class _ReadoutSSE(torch.autograd.Function):
     """Gradients for h, w, b; none for x and mask (their .grad stays None)."""
 
     @staticmethod
-    def forward(ctx, h, x, mask, w, b):
+    def forward(ctx, h, x, mask, w, b, variant):
         _require_gpu(h, x, mask, w, b)
         lib = L.lib()
         T, B, D = h.shape
@@ -29,7 +29,7 @@ class _ReadoutSSE(torch.autograd.Function):
         lik = torch.empty(1, device=h.device, dtype=torch.float32)
         d = L.ReadoutDesc()
         d.struct_size = L.C.sizeof(L.ReadoutDesc)
-        d.latent_dim, d.obs_dim, d.scale, d.rows = D, obs, 1.0 / B, T * B
+        d.latent_dim, d.obs_dim, d.scale, d.variant, d.rows = D, obs, 1.0 / B, variant, T * B
         d.h, d.x, d.mask, d.w, d.b, d.lik = hc.data_ptr(), xc.data_ptr(), mc.data_ptr(), wc.data_ptr(), bc.data_ptr(), lik.data_ptr()
         if need_grad:
             gh = torch.empty_like(hc)
@@ -48,12 +48,13 @@ class _ReadoutSSE(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         gh, gw, gb = ctx.saved_tensors
-        return gh * g, None, None, gw * g, gb * g
+        return gh * g, None, None, gw * g, gb * g, None
 
 
-def masked_sse_readout(h, x, mask, weight, bias):
-    """``sum((x - (h @ weight.T + bias))^2 * mask) / B`` for h (T,B,D), x/mask (T,B,obs); differentiable in h, weight, bias."""
-    return _ReadoutSSE.apply(h, x, mask, weight, bias)
+def masked_sse_readout(h, x, mask, weight, bias, variant=0):
+    """``sum((x - (h @ weight.T + bias))^2 * mask) / B`` for h (T,B,D), x/mask (T,B,obs); differentiable in h, weight, bias.
+    ``variant`` forces a kernel (tuning / tests): ``READOUT_VARIANT_VALU``; 0 = the library chooses."""
+    return _ReadoutSSE.apply(h, x, mask, weight, bias, int(variant))
 
 
 # ----------------------------------------------------------------------------------------------------------------------

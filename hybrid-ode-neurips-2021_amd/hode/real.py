@@ -6,8 +6,6 @@ the flat weight buffer (parameter creation order of the reference)."""
 
 from __future__ import annotations
 
-import os
-
 import torch
 
 from . import _lib as L
@@ -29,7 +27,7 @@ class _RealFixedGrid(torch.autograd.Function):
     """Gradients for y0, theta, wflat; none for t and the action table act (their .grad stays None)."""
 
     @staticmethod
-    def forward(ctx, y0, theta, wflat, t, act, method, perturb, hidden):
+    def forward(ctx, y0, theta, wflat, t, act, method, perturb, hidden, lanes):
         _require_gpu(y0, theta, wflat, t, act)
         lib = L.lib()
         y0c, thc, wc, tc, ac = _f32c(y0), _f32c(theta), _f32c(wflat), _f32c(t), _f32c(act)
@@ -38,29 +36,31 @@ class _RealFixedGrid(torch.autograd.Function):
         assert wc.numel() == 9 * hidden + 2 + 3 * M * M, "flat weight buffer has the wrong length"
         h = torch.empty((tc.numel(), B, D), device=y0.device, dtype=torch.float32)
         d = _desc(y0c, tc, ac, thc, wc, h, method, perturb, hidden)
+        d.lanes_per_patient = lanes
         n = lib.hode_workspace_bytes(d, L.WS_RK_FWD)  # the per-patient dose table
         ws = torch.empty(max(n, 4), device=y0.device, dtype=torch.uint8)
         d.workspace, d.workspace_bytes = ws.data_ptr(), n
         with torch.cuda.device(y0.device):
             L.check(lib.hode_rk_fwd(d, _stream()), "hode_rk_fwd[real]")
         ctx.save_for_backward(h, thc, wc, tc, ac)
-        ctx.meta = (method, int(perturb), int(hidden))
+        ctx.meta = (method, int(perturb), int(hidden), lanes)
         return h
 
     @staticmethod
     def backward(ctx, grad_h):
         h, thc, wc, tc, ac = ctx.saved_tensors
-        method, perturb, H = ctx.meta
+        method, perturb, H, lanes = ctx.meta
         lib = L.lib()
         T, B, D = h.shape
         gh = _f32c(grad_h)
         gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)
         gth = torch.zeros(L.N_THETA, device=h.device, dtype=torch.float32)
         d = _desc(h[0], tc, ac, thc, wc, h, method, perturb, H)
+        d.lanes_per_patient = lanes
         d.grad_h, d.grad_y0, d.grad_theta = gh.data_ptr(), gy0.data_ptr(), gth.data_ptr()
         # matrix-core kernels (D = 20, hidden <= 64): the weight gradients are accumulated on chip into this flat buffer;
-        # the lane-per-patient kernels (HODE_REAL_LAYOUT=t, D = 4) tape the GEMM operands for contract_tape
-        onchip = D == 20 and H <= 64 and os.environ.get("HODE_REAL_LAYOUT", "")[:1] != "t"
+        # the lane-per-patient kernels (lanes_per_patient = 1, D = 4, hidden > 64) tape the GEMM operands for contract_tape
+        onchip = D == 20 and H <= 64 and lanes != 1
         if onchip:
             gw = torch.zeros_like(wc)
             d.grad_w1 = gw.data_ptr()
@@ -70,8 +70,8 @@ class _RealFixedGrid(torch.autograd.Function):
         with torch.cuda.device(h.device):
             L.check(lib.hode_rk_bwd(d, _stream()), "hode_rk_bwd[real]")
         if onchip:
-            return gy0, gth[:3].clone(), gw, None, None, None, None, None
-        return gy0, gth[:3].clone(), contract_tape(ws, T, B, D, H, method), None, None, None, None, None
+            return gy0, gth[:3].clone(), gw, None, None, None, None, None, None
+        return gy0, gth[:3].clone(), contract_tape(ws, T, B, D, H, method), None, None, None, None, None, None
 
 
 def contract_tape(ws, T, B, D, H, method):
@@ -115,8 +115,10 @@ def contract_tape(ws, T, B, D, H, method):
     return torch.cat(parts)
 
 
-def real_solve(y0, theta, wflat, t, act, hidden, method="midpoint", perturb=True):
-    """h (T, B, D).  ``theta`` = (k_immunity, kel, kel2); ``wflat`` = all weights in creation order; ``act`` (Ta, B) doses."""
+def real_solve(y0, theta, wflat, t, act, hidden, method="midpoint", perturb=True, lanes_per_patient=0):
+    """h (T, B, D).  ``theta`` = (k_immunity, kel, kel2); ``wflat`` = all weights in creation order; ``act`` (Ta, B) doses.
+    ``lanes_per_patient`` forces a kernel family (tuning / tests): 1 = one patient per lane, 16 = matrix cores where they
+    exist; 0 = the library chooses."""
     if method not in L.METHODS:
         raise L.HodeConfigError("hode: the real-data rhs is built for the fixed-grid methods (euler, midpoint, rk4); got %r" % (method,))
-    return _RealFixedGrid.apply(y0, theta, wflat, t, act, L.METHODS[method], bool(perturb), int(hidden))
+    return _RealFixedGrid.apply(y0, theta, wflat, t, act, L.METHODS[method], bool(perturb), int(hidden), int(lanes_per_patient))

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define HODE_ABI_VERSION 1
+#define HODE_ABI_VERSION 2
 
 /* right-hand side kinds */
 #define HODE_RHS_ROCHE 0        /* expert PK/PD block + tanh(W y + b)          model.py:515-555 */
@@ -119,9 +119,12 @@ typedef struct hode_solve_desc {
   int32_t n_dose;         /* K doses per patient (ROCHE / NEURAL), equal for all patients (model.py:507) */
   int32_t hidden_dim;     /* NEURAL: 10*D; ROCHE_REAL: MLP hidden width */
   int32_t n_action_times; /* ROCHE_REAL: length of the dose table along time */
-  int32_t lanes_per_patient; /* 0 = library chooses; forces a variant (tuning / tests): 1 = lane per patient,
+  int32_t lanes_per_patient; /* 0 = library chooses; forces a variant (tuning / tests).  ROCHE kinds: 1 = lane per patient,
                                 4 = patient per DPP quad, 16 = MFMA layout (4 lanes strided by 16, D in {8,12,16}),
-                                48 = split layout (expert wave + learned waves per 48 patients, D in {8,12}; default there) */
+                                48 = split layout (expert wave + learned waves per 48 patients, D in {8,12}; default there).
+                                NEURAL / ROCHE_REAL (fixed grid): 1 = the one-patient-per-lane kernels (NEURAL: D in
+                                {6,8,12}), 16 = the matrix-core kernels where they exist (the default there), else the lane
+                                kernels; any other value is HODE_E_UNSUPPORTED */
   int32_t need_theta_grad;   /* backward: also accumulate grad_theta */
 
   const float* t;          /* [T] output grid == step grid (model.py:1072); strictly increasing */
@@ -170,6 +173,8 @@ typedef struct hode_lstm_desc {
   int32_t obs_dim;     /* columns taken from x (and masked); the other I - obs_dim come from a */
   int32_t reverse;     /* 1: walk t = T-1 .. 0 (EncoderLSTM, model.py:420); 0: forward (EncoderLSTMReal) */
   int32_t save_tape;   /* forward: 1 = write the gate/cell tape into workspace for hode_lstm_bwd */
+  int32_t patient_tiles; /* 0 = library chooses; 1..4 forces NT, the 16-patient tiles per workgroup (tuning / tests): honoured
+                            up to 3 with save_tape and 4 without, ignored outside; obs_dim may still clamp the tile */
   const float* x;      /* [T][B][obs_dim] */
   const float* a;      /* [T][B][I - obs_dim] or NULL when I == obs_dim */
   const float* mask;   /* [T][B][obs_dim] or NULL (no masking) */
@@ -192,11 +197,14 @@ typedef struct hode_lstm_desc {
 
 /* Fused readout + masked SSE (reference model.py:1120 x_hat = Linear(D -> obs)(h) and model.py:1179
  * lik = sum((x - x_hat)^2 * mask) / B, plus their autograd backward) without materialising x_hat. */
+#define HODE_READOUT_VARIANT_VALU 1 /* variant: the lane-per-4-outputs kernel even where the matrix-core kernel is the default
+                                      (latent_dim 12, obs_dim 52..80; latent_dim 8, obs_dim 36..48) */
 typedef struct hode_readout_desc {
   uint32_t struct_size;
   int32_t latent_dim;   /* D */
   int32_t obs_dim;      /* obs (multiple of 4, <= 128) */
   float scale;          /* 1 / B: folded into the gradients (lik itself is returned as the plain sum) */
+  int32_t variant;      /* 0 = library chooses; HODE_READOUT_VARIANT_VALU (tuning / tests); else HODE_E_UNSUPPORTED */
   int64_t rows;         /* T * B rows of h / x / mask */
   const float* h;       /* [rows][D] */
   const float* x;       /* [rows][obs] */
@@ -338,7 +346,7 @@ const char* hode_last_error_string(void);
  * only and writes, per (step, stage) instance, the four operands of the weight-gradient GEMMs patient-minor into the
  * workspace: a1t[inst][10D][B], u1t[inst][10D][B], yet[inst][D+1][B], u2t[inst][D][B] (inst = (T-1) * stages); this returns
  * their byte offsets and the caller contracts them: grad_w1 = sum_inst u1t yet^T, grad_b1 = sum u1t, grad_w2 = sum_inst u2t
- * a1t^T, grad_b2 = sum u2t (the one-patient-per-lane kernels, HODE_NEURAL_LAYOUT=t, always work this way). */
+ * a1t^T, grad_b2 = sum u2t (the one-patient-per-lane kernels, lanes_per_patient = 1, always work this way). */
 int hode_neural_tape_offsets(const hode_solve_desc* desc, size_t* out4);
 
 /* HODE_RHS_ROCHE_REAL backward: hode_rk_bwd fills grad_y0 and grad_theta[0..2] (k_immunity, kel, kel2) and tapes the

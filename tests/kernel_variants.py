@@ -112,7 +112,7 @@ def real_kernels(D, H, method, onchip=True):
     """HODE_RHS_ROCHE_REAL.  csrc/hode_real_mf.hip:518 real_mf_supported (D == 20, H <= 64) selects the matrix-core
     kernels (csrc/hode_real.hip:405); their backward folds the weight gradients on chip when the caller hands grad_w1
     (csrc/hode_real_mf.hip:525 `onchip`, :534 real_grad_fold_kernel), else it writes the operand tape.  Everything else
-    (D = 4, D = 20 with H > 64) runs csrc/hode_real.hip:374-382 real_kernel<D, METHOD, BWD>."""
+    (D = 4, D = 20 with H > 64) runs csrc/hode_real.hip:377-385 real_kernel<D, METHOD, BWD>."""
     if D == 20 and 1 <= H <= 64:
         ht = real_mf_ht(H)
         out = ["hode::real_mf_kernel<%d, %d, false, false>" % (ht, method),
@@ -122,7 +122,7 @@ def real_kernels(D, H, method, onchip=True):
 
 
 def choose_lpp(D, lanes, B):
-    """csrc/hode_api.hip:70 choose_lpp."""
+    """csrc/hode_api.hip:66 choose_lpp."""
     can4 = D > 4 and (D - 4) % 4 == 0
     if lanes == 1:
         return 1
@@ -134,8 +134,8 @@ def choose_lpp(D, lanes, B):
 
 
 def roche_layout(D, lanes, T):
-    """csrc/hode_api.hip:126 use_split (D 8 / 12, T <= kSplitMaxT, lanes 48 or 0; the backward needs T >= 2), :113 use_mf
-    (D 8 / 12 / 16 and lanes 16), else the per-dimension lane kernels (:138 dispatch_dim)."""
+    """csrc/hode_api.hip:121 use_split (D 8 / 12, T <= kSplitMaxT, lanes 48 or 0; the backward needs T >= 2), :109 use_mf
+    (D 8 / 12 / 16 and lanes 16), else the per-dimension lane kernels (:132 dispatch_dim)."""
     if D in (8, 12) and T <= SPLIT_MAX_T and T >= 2 and lanes in (0, 48):
         return "split"
     if D in (8, 12, 16) and lanes == 16:
@@ -165,10 +165,10 @@ def roche_fixed(D, lanes, method, ablate, need_theta, tape=True, T=8, B=77):
 
 
 def dopri5_kernels(D, lanes, ablate, need_theta, detach_first_step=True, B=21):
-    """One adaptive solve + its backward.  LPP = choose_lpp (csrc/hode_dopri5.hip:162, :258) -> csrc/hode_dopri5_kernels.hpp
+    """One adaptive solve + its backward.  LPP = choose_lpp (csrc/hode_dopri5.hip:158, :254) -> csrc/hode_dopri5_kernels.hpp
     dp_dispatch (LPP 4 only where (D-4) % 4 == 0) -> dp_launch: the forward's phases 0 / 1 (initial step) and 2 (attempts),
     dp_fwd_kernel<D, LPP, ABLATE, PHASE>; the backward sweep, dp_bwd_kernel<D, LPP, ABLATE, NEED_TH>; and unless the first
-    step size is detached (csrc/hode_dopri5.hip:267) the two passes of its backward, dp_initbwd_kernel<D, LPP, ABLATE,
+    step size is detached (csrc/hode_dopri5.hip:263) the two passes of its backward, dp_initbwd_kernel<D, LPP, ABLATE,
     false, 1> (pass 1 forms a scalar: always NEED_TH = false) and dp_initbwd_kernel<D, LPP, ABLATE, NEED_TH, 2>."""
     lpp, a = choose_lpp(D, lanes, B), _b(ablate)
     out = ["hode::dp_fwd_kernel<%d, %d, %s, %d>" % (D, lpp, a, ph) for ph in (0, 1, 2)]
@@ -179,22 +179,23 @@ def dopri5_kernels(D, lanes, ablate, need_theta, detach_first_step=True, B=21):
     return out
 
 
-def neural_layout(D, env=None):
-    """csrc/hode_neural.hip:355-361 neural_rk: the one-patient-per-lane kernels when HODE_NEURAL_LAYOUT starts with 't'
-    (compiled for D = 6, 8, 12 only, anything else is a configuration error); the matrix-core kernels otherwise."""
-    if env and env[0] == "t":
+def neural_layout(D, lanes=0):
+    """csrc/hode_neural.hip:356-359 neural_rk: the one-patient-per-lane kernels when lanes_per_patient == 1 (:272
+    neural_lanes; compiled for D = 6, 8, 12 only, anything else is a configuration error); the matrix-core kernels for
+    0 and 16."""
+    if lanes == 1:
         assert D in (6, 8, 12), D
         return "lane"
     return "mf"
 
 
-def neural_fixed(D, method, env=None, onchip=True):
+def neural_fixed(D, method, lanes=0, onchip=True):
     """Fixed-grid NeuralODE forward + backward (onchip = the caller hands grad_w1, hode.neural's default).
     mf: csrc/hode_neural_mf.hip:188-203 launch_neural_mf_d: grid ceil(B/16); neural_mf_bwd_kernel<D, M, ONCHIP> with
     ONCHIP = bwd && grad_w1 (:190), and the on-chip backward folds its per-wave partials with neural_grad_fold_kernel<D>
-    (:200).  lane: csrc/hode_neural.hip:318-328 launch_neural: grid ceil(B/64), after transpose_w2_kernel (:362, every
-    call); its backward always writes the operand tapes (csrc/hode_neural.hip:273 neural_onchip)."""
-    if neural_layout(D, env) == "lane":
+    (:200).  lane: csrc/hode_neural.hip:320-330 launch_neural: grid ceil(B/64), after transpose_w2_kernel (:360, every
+    call); its backward always writes the operand tapes (csrc/hode_neural.hip:276 neural_onchip)."""
+    if neural_layout(D, lanes) == "lane":
         return ["hode::transpose_w2_kernel", "hode::neural_fwd_kernel<%d, %d>" % (D, method),
                 "hode::neural_bwd_kernel<%d, %d>" % (D, method)]
     out = ["hode::neural_mf_fwd_kernel<%d, %d>" % (D, method),
@@ -202,8 +203,13 @@ def neural_fixed(D, method, env=None, onchip=True):
     return out + (["hode::neural_grad_fold_kernel<%d>" % D] if onchip else [])
 
 
+def neural_lanes(case):
+    """lanes_per_patient that forces a neural case's layout: 1 for "lane"; "mf" is what the library chooses (0)."""
+    return 1 if case["layout"] == "lane" else 0
+
+
 def neural_grid(B, layout):
-    """Workgroups of one launch: csrc/hode_neural_mf.hip:189 (16 patients per wave), csrc/hode_neural.hip:319 (64)."""
+    """Workgroups of one launch: csrc/hode_neural_mf.hip:189 (16 patients per wave), csrc/hode_neural.hip:321 (64)."""
     return (B + 15) // 16 if layout == "mf" else (B + 63) // 64
 
 
@@ -237,28 +243,28 @@ def choose_nt(B, save_tape):
     return best
 
 
-def lstm_geom(H, obs, B, save_tape, nt_env=None):
-    """csrc/hode_lstm.hip:82-124 lstm_geom -> (Hp, TPW, fTPW, fNW, NT): Hp the next compiled size, TPW = Hp / 16; the
+def lstm_geom(H, obs, B, save_tape, patient_tiles=0):
+    """csrc/hode_lstm.hip:82-122 lstm_geom -> (Hp, TPW, fTPW, fNW, NT): Hp the next compiled size, TPW = Hp / 16; the
     forward runs fNW = 4 waves of TPW tiles for TPW <= 5, else 8 waves of TPW / 2 (csrc/hode_lstm_tpw.hip:18-19); NT from
-    choose_nt, the HODE_LSTM_NT override inside the same bound (:96-99), then the staging clamp 16 NT obs <= 5120 (:110)."""
+    choose_nt, the patient_tiles override inside the same bound (:96-97), then the staging clamp 16 NT obs <= 5120 (:106)."""
     Hp = next(v for v in LSTM_SIZES if H <= v)
     tpw = Hp // 16
     fnw = 4 if tpw <= 5 else 8
     nt = choose_nt(B, save_tape)
-    if nt_env is not None and 1 <= nt_env <= (3 if save_tape else 4):
-        nt = nt_env
+    if 1 <= patient_tiles <= (3 if save_tape else 4):
+        nt = patient_tiles
     while nt > 1 and 16 * nt * obs > 5120:
         nt -= 1
     return Hp, tpw, 4 * tpw // fnw, fnw, nt
 
 
-def lstm_kernels(H, obs, B, save_tape, nt_env=None):
-    """hode_lstm_fwd (csrc/hode_lstm.hip:171 lstm_pack_kernel, then csrc/hode_lstm_tpw.hip:33-35
+def lstm_kernels(H, obs, B, save_tape, patient_tiles=0):
+    """hode_lstm_fwd (csrc/hode_lstm.hip:169 lstm_pack_kernel, then csrc/hode_lstm_tpw.hip:33-35
     lstm_fwd_kernel<NT, fTPW, fNW, VEC4 = obs % 4 == 0>); with the tape (hode.lstm.lstm_encode) also hode_lstm_bwd
-    (csrc/hode_lstm.hip:219 lstm_pack_hh_kernel, csrc/hode_lstm_tpw.hip:47-49 lstm_bwd_kernel<NT, TPW, FLAT = H == 16 TPW>)
-    and hode_lstm_fill_operand (csrc/hode_lstm.hip:270-276 lstm_fill_operand_kernel<VEC4>: obs % 4 == 0 and 16-byte
+    (csrc/hode_lstm.hip:217 lstm_pack_hh_kernel, csrc/hode_lstm_tpw.hip:47-49 lstm_bwd_kernel<NT, TPW, FLAT = H == 16 TPW>)
+    and hode_lstm_fill_operand (csrc/hode_lstm.hip:268-274 lstm_fill_operand_kernel<VEC4>: obs % 4 == 0 and 16-byte
     aligned x / mask / h_prev, which fresh tensors are)."""
-    _, tpw, ftpw, fnw, nt = lstm_geom(H, obs, B, save_tape, nt_env)
+    _, tpw, ftpw, fnw, nt = lstm_geom(H, obs, B, save_tape, patient_tiles)
     vec4 = _b(obs % 4 == 0)
     out = ["hode::lstm_pack_kernel", "hode::lstm_fwd_kernel<%d, %d, %d, %s>" % (nt, ftpw, fnw, vec4)]
     if save_tape:
@@ -267,14 +273,14 @@ def lstm_kernels(H, obs, B, save_tape, nt_env=None):
     return out
 
 
-def lstm_workspace_bytes(T, B, I, H, obs, save_tape, nt_env=None):
-    """csrc/hode_lstm.hip:152-158 hode_lstm_workspace_bytes from the restated geometry: [packed W (4 KQ4 TPW 64 4 floats,
+def lstm_workspace_bytes(T, B, I, H, obs, save_tape, patient_tiles=0):
+    """csrc/hode_lstm.hip:150-156 hode_lstm_workspace_bytes from the restated geometry: [packed W (4 KQ4 TPW 64 4 floats,
     Kq = ceil((I + Hp + 1) / 4), KQ4 = ceil(Kq / 4)) | packed W_hh^T | tape (T nblk 4 TPW NT 5 64 floats)], 256-aligned."""
-    Hp, tpw, _, _, nt = lstm_geom(H, obs, B, save_tape, nt_env)
+    Hp, tpw, _, _, nt = lstm_geom(H, obs, B, save_tape, patient_tiles)
     al = lambda x: (x + 255) // 256 * 256  # noqa: E731
     kq = (I + Hp + 1 + 3) // 4
     kq4 = (kq + 3) // 4
-    # csrc/hode_lstm.hip:113-115: the LDS bound of the launched (clamped) tile, 0 = unsupported
+    # csrc/hode_lstm.hip:111-113: the LDS bound of the launched (clamped) tile, 0 = unsupported
     if 2 * 4 * kq * (16 * nt + (16 if (16 * nt) % 32 == 0 else 0)) * 4 > 160 * 1024:
         return 0
     n = al(4 * kq4 * tpw * 64 * 4 * 4)
@@ -284,29 +290,32 @@ def lstm_workspace_bytes(T, B, I, H, obs, save_tape, nt_env=None):
     return n
 
 
-def readout_mf(latent, obs, valu=False):
+READOUT_VARIANT_VALU = 1  # include/hode.h HODE_READOUT_VARIANT_VALU
+
+
+def readout_mf(latent, obs, variant=0):
     """csrc/hode_readout.hip:292-295 readout_mf: the matrix-core kernel for (12, 48 < obs <= 80) and (8, 32 < obs <= 48),
-    unless HODE_READOUT_VALU is set."""
-    if valu:
+    unless the descriptor's variant is HODE_READOUT_VARIANT_VALU."""
+    if variant == READOUT_VARIANT_VALU:
         return False
     return (latent == 12 and 48 < obs <= 80) or (latent == 8 and 32 < obs <= 48)
 
 
-def readout_kernels(latent, obs, grad, valu=False):
-    """csrc/hode_readout.hip:328-351 hode_readout_sse: readout_mf_kernel<12, 5, GRAD> / <8, 3, GRAD> or
+def readout_kernels(latent, obs, grad, variant=0):
+    """csrc/hode_readout.hip:330-353 hode_readout_sse: readout_mf_kernel<12, 5, GRAD> / <8, 3, GRAD> or
     readout_sse_kernel<D, GRAD> (GRAD = grad_h given), then readout_fold_kernel (grid P with the gradient, 1 without)."""
     g = _b(grad)
-    if readout_mf(latent, obs, valu):
+    if readout_mf(latent, obs, variant):
         k = "hode::readout_mf_kernel<%s, %s>" % ("12, 5" if latent == 12 else "8, 3", g)
     else:
         k = "hode::readout_sse_kernel<%d, %s>" % (latent, g)
     return [k, "hode::readout_fold_kernel"]
 
 
-def readout_waves(rows, obs, latent, valu=False):
+def readout_waves(rows, obs, latent, variant=0):
     """csrc/hode_readout.hip:297-301 readout_waves: 16 rows per wave-iteration on the matrix cores, 64 / (obs / 4) on the
     lanes; at most 2048 waves."""
-    rpi = 16 if readout_mf(latent, obs, valu) else 64 // (obs // 4)
+    rpi = 16 if readout_mf(latent, obs, variant) else 64 // (obs // 4)
     return max(1, min((rows + rpi - 1) // rpi, 2048))
 
 
@@ -332,7 +341,7 @@ def roche_body(ablate, theta0, theta1, K):
     csrc/hode_rk_kernels.hpp:122-126 (rk_fwd_kernel), :299-302 (rk_bwd_kernel); csrc/hode_rk_split.hip:1115-1118
     (split_bwd_kernel), :1123-1126 (split_fwd_kernel); csrc/hode_rk_mf.hip:245-248 (mf_fwd_kernel), :498-501
     (mf_bwd_kernel); csrc/hode_dopri5_kernels.hpp:886-889 (dp_persist_kernel), :896-906 (dp_fwd_kernel; its attempt
-    launches take hill2 from the host's read-back of the same comparison, csrc/hode_dopri5.hip:178-184), :1395-1403
+    launches take hill2 from the host's read-back of the same comparison, csrc/hode_dopri5.hip:174-180), :1395-1403
     (dp_bwd_kernel), :1536-1539 (dp_initbwd_kernel).  ABLATE forces hill2: the ablate rhs has no Hill terms."""
     hill2 = bool(ablate) or (theta0 == 2.0 and theta1 == 2.0)
     if hill2:
@@ -565,7 +574,7 @@ LSTM_OBS_VEC4, LSTM_OBS_ODD = 20, 23
 def _lstm_cases():
     """Per padded hidden size (TPW): the tape path (lstm_encode) at NT 1, 2, 3 once with H = 16 TPW and obs % 4 != 0,
     once with H = 16 TPW - 3 and obs % 4 == 0 -- every (NT, FLAT) backward and (NT, VEC4) forward -- and the no-tape path
-    (lstm_final_state) at NT = 4 with both obs; NT forced by HODE_LSTM_NT on a batch ragged against 16 NT, T = 3 or 4.
+    (lstm_final_state) at NT = 4 with both obs; NT forced by patient_tiles on a batch ragged against 16 NT, T = 3 or 4.
     Then NT chosen by choose_nt from the batch size alone (1: B = 100; 2: 4097; 3: 8193; 4: 12289 without a tape), the
     staging clamp (obs = 100 lowers a forced NT = 4 to 3, at the largest hidden size too), and B = 1 / T = 1 calls."""
     out = []
@@ -588,7 +597,7 @@ def _lstm_cases():
 
 def _readout_cases():
     """Each latent dimension of the lane kernel, both sides of every readout_mf window edge (D 12: 48 | 52, 80 | 84; D 8:
-    32 | 36, 48 | 52), the window with HODE_READOUT_VALU, row counts at the 2048-wave cap; the MLP readout at both DL;
+    32 | 36, 48 | 52), the window with the lane kernel forced (variant), row counts at the 2048-wave cap; the MLP readout at both DL;
     then a single row.  Every case runs the call with and without the gradient (GRAD = true / false)."""
     out = []
     for D, obs, T, B in ((4, 20, 3, 21), (4, 128, 3, 33), (6, 20, 4, 17), (6, 92, 3, 21), (8, 32, 3, 19), (8, 36, 3, 23),
@@ -604,8 +613,8 @@ def _readout_cases():
 
 
 NEURAL_DIMS = (4, 6, 8, 10, 12, 14)  # csrc/hode_neural_mf.hip:220-227 launch_neural_mf (check_neural: even, 4..14)
-NEURAL_LANE_DIMS = (6, 8, 12)        # csrc/hode_neural.hip:360-368
-READOUT_LATENT = (4, 6, 8, 12)       # csrc/hode_readout.hip:340-345
+NEURAL_LANE_DIMS = (6, 8, 12)        # csrc/hode_neural.hip:358-366
+READOUT_LATENT = (4, 6, 8, 12)       # csrc/hode_readout.hip:342-347
 NEW_FAMILIES = ("neural", "neural_dopri5", "lstm", "readout", "readout_mlp")  # CASES families of the kernels below
 
 
@@ -615,9 +624,9 @@ def instantiations():
     out = set()
     for m in METHODS.values():
         for D in NEURAL_DIMS:
-            out.update(neural_fixed(D, m, None, True) + neural_fixed(D, m, None, False))
+            out.update(neural_fixed(D, m, 0, True) + neural_fixed(D, m, 0, False))
         for D in NEURAL_LANE_DIMS:
-            out.update(neural_fixed(D, m, "t"))
+            out.update(neural_fixed(D, m, 1))
     for D in NEURAL_DOPRI5_DIMS:
         out.update(neural_dopri5_kernels(D, 1, False))
     for tpw in LSTM_TPWS:
@@ -658,14 +667,14 @@ def kernels(case):
     if f == "dopri5":
         return dopri5_kernels(case["D"], case["lanes"], case["ablate"], case["need_theta"], case["detach"], DOPRI5_N)
     if f == "neural":
-        return neural_fixed(case["D"], METHODS[case["method"]], "t" if case["layout"] == "lane" else None, case["onchip"])
+        return neural_fixed(case["D"], METHODS[case["method"]], neural_lanes(case), case["onchip"])
     if f == "neural_dopri5":
         return neural_dopri5_kernels(case["D"], case["T"] - 1, case["detach"])
     if f == "lstm":
-        return lstm_kernels(case["H"], case["obs"], case["B"], case["tape"], case["nt"])
+        return lstm_kernels(case["H"], case["obs"], case["B"], case["tape"], case["nt"] or 0)
     if f == "readout":
-        return readout_kernels(case["D"], case["obs"], True, case["valu"]) + readout_kernels(case["D"], case["obs"], False,
-                                                                                           case["valu"])[:1]
+        v = int(case["valu"])  # valu=True: READOUT_VARIANT_VALU
+        return readout_kernels(case["D"], case["obs"], True, v) + readout_kernels(case["D"], case["obs"], False, v)[:1]
     if f == "readout_mlp":
         return readout_mlp_kernels(case["D"], True) + readout_mlp_kernels(case["D"], False)[:1]
     raise ValueError(f)
@@ -690,7 +699,7 @@ for _D in (8, 12):
         for _nt in ("false", "true"):
             UNREACHABLE["hode::split_bwd_kernel<%d, 0, %s, %s, true>" % (_D, _a, _nt)] = _NO_EULER_TAPE
 _NO_PERSIST = ("the persistent attempt loop is launched only by builds with -DHODE_DP_EXPERIMENTS and HODE_DP_PERSIST=1 "
-               "(csrc/hode_dopri5.hip:195-197); the product build compiles it but never launches it")
+               "(csrc/hode_dopri5.hip:191-193); the product build compiles it but never launches it")
 for _D in (8, 12):
     for _a in ("false", "true"):
         UNREACHABLE["hode::dp_persist_kernel<%d, %s>" % (_D, _a)] = _NO_PERSIST
@@ -705,7 +714,7 @@ OTHER_KERNELS = {
     # the metric kernels have a case table of their own (tests/metric_cases.py, guarded by tests/test_metric_case_coverage.py)
     "hode::crps_kernel": "tests/test_hip_metric_cases.py::test_crps_case",
     "hode::mc_kl_exp_kernel": "tests/test_hip_metric_cases.py::test_mckl_case",
-    # the weight / theta gradient fold behind the Roche lane-kernel backward (csrc/hode_api.hip:255), the Roche dopri5
-    # backward (csrc/hode_dopri5.hip:264, :274) and hode_real.hip (:412): every lane / dopri5 / real_kernel case runs it
+    # the weight / theta gradient fold behind the Roche lane-kernel backward (csrc/hode_api.hip:249), the Roche dopri5
+    # backward (csrc/hode_dopri5.hip:260, :270) and hode_real.hip (:412): every lane / dopri5 / real_kernel case runs it
     "hode::fold_partials_kernel": "tests/test_hip_kernel_variants.py::test_roche_fixed_grid",
 }

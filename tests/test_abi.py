@@ -10,6 +10,11 @@ import abi_checks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
+# the tuning variables the library and its wrappers once read from the environment, each at the value that flipped a
+# decision: kernel variants are selected through descriptor fields and keyword arguments, and these must change nothing
+STALE_ENV = {"HODE_PPW": "1", "HODE_RK_LAYOUT": "q", "HODE_NEURAL_LAYOUT": "t", "HODE_REAL_LAYOUT": "t", "HODE_LSTM_NT": "1",
+             "HODE_READOUT_VALU": "1", "HODE_LSTM_GEMM_MN": "1", "HODE_LSTM_SERIAL_FILL": "1"}
+
 
 @pytest.fixture(scope="module")
 def lib():
@@ -80,6 +85,55 @@ def test_workspace_query(lib):
     d.latent_dim = 20  # no split layout for D = 20: quad
     n20 = lib.hode_workspace_bytes(d, L.WS_RK_BWD)
     assert n20 % ((16 * 20 + 16 + 15) * 4) == 0
+
+
+def _variant_sizes(lib, forced):
+    """Workspace sizes of five calls whose kernel variant has a switch; `forced` selects the non-default variant through
+    the descriptor field (quad Roche layout, lane-per-patient neural / real kernels, NT = 1, the lane readout kernel)."""
+    import ctypes as C
+    from hode import _lib as L
+    buf = (C.c_float * 4)()
+    out = {}
+    d = L.new_solve_desc()
+    d.rhs_kind, d.method, d.batch, d.latent_dim, d.n_times = L.RHS_ROCHE, L.METHODS["rk4"], 10000, 12, 100
+    d.lanes_per_patient = 4 if forced else 0
+    out["roche"] = lib.hode_workspace_bytes(d, L.WS_RK_BWD)
+    d = L.new_solve_desc()
+    d.rhs_kind, d.method, d.batch, d.latent_dim, d.n_times, d.hidden_dim = L.RHS_NEURAL, L.METHODS["rk4"], 10000, 8, 100, 80
+    d.grad_w1 = C.addressof(buf)  # never dereferenced: only selects the on-chip layout
+    d.lanes_per_patient = 1 if forced else 0
+    out["neural"] = lib.hode_workspace_bytes(d, L.WS_RK_BWD)
+    d = L.new_solve_desc()
+    d.rhs_kind, d.method, d.batch, d.latent_dim, d.n_times = L.RHS_ROCHE_REAL, L.METHODS["midpoint"], 10000, 20, 100
+    d.hidden_dim, d.n_action_times = 17, 100
+    d.grad_w1 = C.addressof(buf)
+    d.lanes_per_patient = 1 if forced else 0
+    out["real"] = lib.hode_workspace_bytes(d, L.WS_RK_BWD)
+    d = L.new_lstm_desc()
+    d.seq_len, d.batch, d.input_dim, d.hidden_dim, d.obs_dim, d.save_tape = 3, 4097, 21, 40, 20, 1
+    d.patient_tiles = 1 if forced else 0
+    out["lstm"] = lib.hode_lstm_workspace_bytes(d)
+    d = L.ReadoutDesc()
+    d.struct_size = C.sizeof(L.ReadoutDesc)
+    d.latent_dim, d.obs_dim, d.rows = 12, 52, 1000
+    d.variant = L.READOUT_VARIANT_VALU if forced else 0
+    out["readout"] = lib.hode_readout_workspace_bytes(d)
+    assert all(v > 0 for v in out.values()), out
+    return out
+
+
+def test_variants_follow_the_descriptor_not_the_environment(lib, monkeypatch):
+    """No launch: with every former tuning variable set to the value that used to flip a decision, the workspace sizes
+    are exactly those of a clean environment; the descriptor fields are what selects a variant (each forced size differs)."""
+    for name in STALE_ENV:
+        monkeypatch.delenv(name, raising=False)
+    clean, forced = _variant_sizes(lib, False), _variant_sizes(lib, True)
+    for name, value in STALE_ENV.items():
+        monkeypatch.setenv(name, value)
+    assert _variant_sizes(lib, False) == clean
+    assert _variant_sizes(lib, True) == forced
+    for k in clean:
+        assert forced[k] != clean[k], k
 
 
 def test_tape_flag_needs_its_workspace(lib):

@@ -181,12 +181,13 @@ def _real_problem(D, H, method, perturb=True, B=37, Ta=12, t0=4, t=None):
     return dict(y0=y0, a=a, t=t, cot=cot, wflat=wflat, theta=theta, perturb=perturb), ref
 
 
-def _real_gpu(p, H, method, dev):
+def _real_gpu(p, H, method, dev, lanes=0):
     from hode.real import real_solve
     wflat = p["wflat"].to(dev).requires_grad_(True)
     theta = p["theta"].to(dev).requires_grad_(True)
     y0 = p["y0"].to(dev).requires_grad_(True)
-    h = real_solve(y0, theta, wflat, p["t"].to(dev), p["a"][..., 0].to(dev), H, method=method, perturb=p["perturb"])
+    h = real_solve(y0, theta, wflat, p["t"].to(dev), p["a"][..., 0].to(dev), H, method=method, perturb=p["perturb"],
+                   lanes_per_patient=lanes)
     (h * p["cot"].to(dev)).sum().backward()
     torch.cuda.synchronize()
     return dict(h=h.detach(), gy0=y0.grad, gw=wflat.grad, gth=theta.grad)
@@ -218,8 +219,7 @@ def _real_gpu_tape_backward(p, H, method, dev):
 
 
 @pytest.mark.parametrize("case", _family("real"), ids=kv.case_id)
-def test_real(case, monkeypatch):
-    monkeypatch.delenv("HODE_REAL_LAYOUT", raising=False)
+def test_real(case):
     dev = _dev()
     D, H, method = case["D"], case["H"], case["method"]
     p, ref = _real_problem(D, H, method)
@@ -229,8 +229,7 @@ def test_real(case, monkeypatch):
         assert _rel(got[k], ref[k]) <= 1e-4, (k, _rel(got[k], ref[k]))
     if D == 20 and H > 64:
         # past the matrix-core range the default takes hode_real.hip: the same numbers as forcing that layout
-        monkeypatch.setenv("HODE_REAL_LAYOUT", "t")
-        forced = _real_gpu(p, H, method, dev)
+        forced = _real_gpu(p, H, method, dev, lanes=1)
         for k in ("h", "gy0", "gw", "gth"):
             assert torch.equal(got[k], forced[k]), k
 
@@ -360,8 +359,7 @@ HILL_ULP_TOL = 1e-5  # rel-L2 between the general body at HillCure = 2 + 2^-22 a
 
 
 @pytest.mark.parametrize("case", _family("roche"), ids=kv.case_id)
-def test_roche_fixed_grid(case, monkeypatch, record_property):
-    monkeypatch.delenv("HODE_RK_LAYOUT", raising=False)  # lanes = 0 must take the layout kv.roche_layout restates
+def test_roche_fixed_grid(case, record_property):
     dev = _dev()
     D, method, ablate = case["D"], case["method"], case["ablate"]
     p, ref = _roche_problem(D, method, ablate, _problem_key(case))
@@ -527,12 +525,13 @@ def _neural_params(p, dev):
     return [x.detach().clone().to(dev).requires_grad_(True) for x in (n[0].weight, n[0].bias, n[2].weight, n[2].bias)]
 
 
-def _neural_gpu(p, method, perturb, dev):
+def _neural_gpu(p, method, perturb, dev, lanes=0):
     """hode.neural.neural_solve + autograd: the on-chip backward (mf) or the tape backward of the lane layout."""
     from hode.neural import neural_solve
     prm = _neural_params(p, dev)
     y0 = p["y0"].to(dev).requires_grad_(True)
-    h = neural_solve(y0, *prm, p["t"].to(dev), p["dosage"].to(dev), p["times"].to(dev), method=method, perturb=perturb)
+    h = neural_solve(y0, *prm, p["t"].to(dev), p["dosage"].to(dev), p["times"].to(dev), method=method, perturb=perturb,
+                     lanes_per_patient=lanes)
     (h * p["cot"].to(dev)).sum().backward()
     torch.cuda.synchronize()
     return dict(h=h.detach(), gy0=y0.grad, gw1=prm[0].grad, gb1=prm[1].grad, gw2=prm[2].grad, gb2=prm[3].grad)
@@ -566,15 +565,11 @@ NEURAL_GRADS = ("gy0", "gw1", "gb1", "gw2", "gb2")
 
 
 @pytest.mark.parametrize("case", _family("neural"), ids=kv.case_id)
-def test_neural_fixed_grid(case, monkeypatch, record_property):
+def test_neural_fixed_grid(case, record_property):
     """neural_mf_* (on-chip and tape-writing backward) and the lane layout against oracle.rhs.NeuralRHS in fp64 with
     oracle.solvers.odeint, perturb included: trajectory 2e-5 (1 + max|h|), every gradient rel-L2 1e-4.  The tape backward is
     also compared with the on-chip backward on the same inputs (_tape_same_as_onchip)."""
     dev = _dev()
-    if case["layout"] == "lane":
-        monkeypatch.setenv("HODE_NEURAL_LAYOUT", "t")
-    else:
-        monkeypatch.delenv("HODE_NEURAL_LAYOUT", raising=False)
     method, perturb = case["method"], case["perturb"]
     p = _neural_problem(case)
     ref = _neural_ref(p, method, perturb)
@@ -583,7 +578,7 @@ def test_neural_fixed_grid(case, monkeypatch, record_property):
         q["times"][:, 0] = torch.nextafter(q["times"][:, 0], torch.tensor(1e9))
         assert (_neural_ref(q, method, perturb)["h"] - ref["h"]).abs().max() > 1e-3
     got = _neural_gpu_tape_backward(p, method, perturb, dev) if not case["onchip"] and case["layout"] == "mf" \
-        else _neural_gpu(p, method, perturb, dev)
+        else _neural_gpu(p, method, perturb, dev, kv.neural_lanes(case))
     assert torch.equal(got["h"][0].cpu(), p["y0"])
     _traj_ok(got["h"], ref["h"])
     record_property("err_h", (got["h"].double().cpu() - ref["h"]).abs().max().item() / (1 + ref["h"].abs().max().item()))
@@ -674,7 +669,7 @@ def _lstm_problem(case):
     return enc, x, a, m, cot
 
 
-def _lstm_fwd_tape(x, a, m, w, dev):
+def _lstm_fwd_tape(x, a, m, w, dev, nt):
     """hode_lstm_fwd with save_tape = 1 (the forward lstm_encode runs), for its final c."""
     import hode
     from hode import _lib as L
@@ -684,7 +679,7 @@ def _lstm_fwd_tape(x, a, m, w, dev):
     h = torch.empty((B, H), device=dev)
     c = torch.empty((B, H), device=dev)
     d = _desc(x, a, m, *w, True, True)
-    d.h_out, d.c_out = h.data_ptr(), c.data_ptr()
+    d.patient_tiles, d.h_out, d.c_out = nt, h.data_ptr(), c.data_ptr()
     n = lib.hode_lstm_workspace_bytes(d)
     assert n > 0
     ws = torch.empty(n, device=dev, dtype=torch.uint8)
@@ -714,17 +709,14 @@ def _lstm_fill_operand_ok(x, a, m, w, dev):
 
 
 @pytest.mark.parametrize("case", _family("lstm"), ids=kv.case_id)
-def test_lstm(case, monkeypatch, record_property):
+def test_lstm(case, record_property):
     """lstm_fwd_kernel / lstm_bwd_kernel / lstm_fill_operand_kernel against oracle.encoder.EncoderLSTMOracle in fp64: final h
     to 2e-5 and c to 5e-5 (absolute, test_hip_lstm's bounds), grad_w_ih / grad_w_hh / grad_b_ih / grad_b_hh of sum(h * cot)
     rel-L2 1e-4.  Tape cases go through hode.lstm.lstm_encode (and the ABI forward for c), the others through
-    lstm_final_state; NT from HODE_LSTM_NT where the case forces it, else from the batch size."""
+    lstm_final_state; NT from patient_tiles where the case forces it, else from the batch size."""
     from hode.lstm import lstm_encode, lstm_final_state
     dev = _dev()
-    if case["nt"] is None:
-        monkeypatch.delenv("HODE_LSTM_NT", raising=False)
-    else:
-        monkeypatch.setenv("HODE_LSTM_NT", str(case["nt"]))
+    nt = case["nt"] or 0
     enc, x, a, m, cot = _lstm_problem(case)
     e64 = copy.deepcopy(enc).double()
     h64, c64 = e64.final_hidden(x.double(), a.double(), m.double())
@@ -733,9 +725,9 @@ def test_lstm(case, monkeypatch, record_property):
     w = [q.detach().to(dev) for q in (p.weight_ih_l0, p.weight_hh_l0, p.bias_ih_l0, p.bias_hh_l0)]
     xd, ad, md = x.to(dev), a.to(dev), m.to(dev)
     if case["tape"]:
-        h, c = _lstm_fwd_tape(xd, ad, md, w, dev)
+        h, c = _lstm_fwd_tape(xd, ad, md, w, dev, nt)
         wg = [q.clone().requires_grad_(True) for q in w]
-        he = lstm_encode(xd, ad, md, *wg, reverse=True)
+        he = lstm_encode(xd, ad, md, *wg, reverse=True, patient_tiles=nt)
         assert torch.equal(he.detach(), h)
         (he * cot.to(dev)).sum().backward()
         q64 = e64.lstm
@@ -746,7 +738,7 @@ def test_lstm(case, monkeypatch, record_property):
             assert e <= 1e-4, (name, e)
         _lstm_fill_operand_ok(xd, ad, md, w, dev)
     else:
-        h, c = lstm_final_state(xd, ad, md, *w, reverse=True)
+        h, c = lstm_final_state(xd, ad, md, *w, reverse=True, patient_tiles=nt)
     eh = (h.double().cpu() - h64.detach()).abs().max().item()
     ec = (c.double().cpu() - c64.detach()).abs().max().item()
     record_property("err_h", eh)
@@ -763,15 +755,12 @@ def _lik_same(lik, lik0, record_property):
 
 
 @pytest.mark.parametrize("case", _family("readout"), ids=kv.case_id)
-def test_readout(case, monkeypatch, record_property):
+def test_readout(case, record_property):
     """readout_sse_kernel / readout_mf_kernel (GRAD true and false) + readout_fold_kernel against the fp64 torch expression
     (test_hip_readout's bounds: loss rel 2e-5, gradients rel-L2 2e-5)."""
     from hode.readout import masked_sse_readout
     dev = _dev()
-    if case["valu"]:
-        monkeypatch.setenv("HODE_READOUT_VALU", "1")
-    else:
-        monkeypatch.delenv("HODE_READOUT_VALU", raising=False)
+    variant = kv.READOUT_VARIANT_VALU if case["valu"] else 0
     D, obs, T, B = case["D"], case["obs"], case["T"], case["B"]
     gen = torch.Generator().manual_seed(D * 1000 + obs + B)
     torch.manual_seed(obs + T)
@@ -785,10 +774,10 @@ def test_readout(case, monkeypatch, record_property):
     ref.backward()
     hg = h.to(dev).requires_grad_(True)
     wg, bg = lin.weight.detach().to(dev).requires_grad_(True), lin.bias.detach().to(dev).requires_grad_(True)
-    lik = masked_sse_readout(hg, x.to(dev), m.to(dev), wg, bg)
+    lik = masked_sse_readout(hg, x.to(dev), m.to(dev), wg, bg, variant=variant)
     lik.backward()
     with torch.no_grad():
-        lik0 = masked_sse_readout(hg.detach(), x.to(dev), m.to(dev), wg.detach(), bg.detach())
+        lik0 = masked_sse_readout(hg.detach(), x.to(dev), m.to(dev), wg.detach(), bg.detach(), variant=variant)
     e = abs(lik.item() - ref.item()) / abs(ref.item())
     record_property("err_lik", e)
     assert e <= READOUT_TOL, e

@@ -45,11 +45,10 @@ def test_final_state_matches_oracle(obs, H, B, T):
 
 
 @pytest.mark.parametrize("nt", [1, 2, 3, 4])
-def test_every_patient_tile_variant(nt, monkeypatch):
+def test_every_patient_tile_variant(nt):
     """The library picks the patient tile (16*NT) from the batch size; force each compiled variant on a ragged batch."""
     from hode.lstm import lstm_final_state
     dev = _dev()
-    monkeypatch.setenv("HODE_LSTM_NT", str(nt))
     obs, H, B, T = 80, 160, 16 * nt * 3 + 5, 4
     torch.manual_seed(nt)
     enc = EncoderLSTMOracle(obs + 1, H, 12)
@@ -58,7 +57,7 @@ def test_every_patient_tile_variant(nt, monkeypatch):
         h_o, c_o = enc.final_hidden(x, a, m)
     p = enc.lstm
     h, c = lstm_final_state(x.to(dev), a.to(dev), m.to(dev), p.weight_ih_l0.to(dev), p.weight_hh_l0.to(dev),
-                            p.bias_ih_l0.to(dev), p.bias_hh_l0.to(dev), reverse=True)
+                            p.bias_ih_l0.to(dev), p.bias_hh_l0.to(dev), reverse=True, patient_tiles=nt)
     assert (h.cpu() - h_o).abs().max().item() <= 2e-5 and (c.cpu() - c_o).abs().max().item() <= 5e-5
 
 
@@ -102,10 +101,9 @@ def test_backward_matches_oracle_autograd(obs, H, B, T):
 
 
 @pytest.mark.parametrize("nt", [1, 2, 3])
-def test_backward_every_tile_variant(nt, monkeypatch):
+def test_backward_every_tile_variant(nt):
     from hode.lstm import lstm_encode
     dev = _dev()
-    monkeypatch.setenv("HODE_LSTM_NT", str(nt))
     obs, H, B, T = 80, 160, 16 * nt * 2 + 3, 4
     torch.manual_seed(nt + 10)
     enc = EncoderLSTMOracle(obs + 1, H, 12)
@@ -115,7 +113,7 @@ def test_backward_every_tile_variant(nt, monkeypatch):
     (h_o * cot).sum().backward()
     p = enc.lstm
     prm = [q.detach().clone().to(dev).requires_grad_(True) for q in (p.weight_ih_l0, p.weight_hh_l0, p.bias_ih_l0, p.bias_hh_l0)]
-    h = lstm_encode(x.to(dev), a.to(dev), m.to(dev), *prm, reverse=True)
+    h = lstm_encode(x.to(dev), a.to(dev), m.to(dev), *prm, reverse=True, patient_tiles=nt)
     (h * cot.to(dev)).sum().backward()
     for q, ref in zip(prm, (p.weight_ih_l0, p.weight_hh_l0, p.bias_ih_l0, p.bias_hh_l0)):
         assert float((q.grad.cpu().double() - ref.grad.double()).norm() / ref.grad.double().norm()) <= 1e-4

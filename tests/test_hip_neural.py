@@ -23,16 +23,13 @@ def _rel(a, b):
 @pytest.mark.parametrize("layout", ["matrix-cores", "lane-per-patient"])
 @pytest.mark.parametrize("D", [6, 8, 12])
 @pytest.mark.parametrize("method", ["euler", "midpoint", "rk4"])
-def test_neural_forward_backward_vs_oracle(D, method, layout, monkeypatch):
-    """Both kernel families behind HODE_RHS_NEURAL: hode_neural_mf.hip (default) and hode_neural.hip (HODE_NEURAL_LAYOUT=t);
+def test_neural_forward_backward_vs_oracle(D, method, layout):
+    """Both kernel families behind HODE_RHS_NEURAL: hode_neural_mf.hip (default) and hode_neural.hip (lanes_per_patient=1);
     N = 70 leaves the last 16-patient wave of the matrix-core layout partly empty."""
     from hode import synth
     from hode.neural import neural_solve
     dev = _dev()
-    if layout == "lane-per-patient":
-        monkeypatch.setenv("HODE_NEURAL_LAYOUT", "t")
-    else:
-        monkeypatch.delenv("HODE_NEURAL_LAYOUT", raising=False)
+    lanes = 1 if layout == "lane-per-patient" else 0
     N, T = 70, 14
     inp = synth.solver_inputs(N, T, D, seed=D)
     inp["z0"] = inp["z0"] * 30.0
@@ -46,7 +43,7 @@ def test_neural_forward_backward_vs_oracle(D, method, layout, monkeypatch):
     prm = [p.detach().clone().to(dev).requires_grad_(True) for p in (f.ml_net[0].weight, f.ml_net[0].bias, f.ml_net[2].weight, f.ml_net[2].bias)]
     y0g = inp["z0"].to(dev).requires_grad_(True)
     dosage, times = dose_schedule(inp["actions"], synth.STEP)
-    h = neural_solve(y0g, *prm, inp["t"].to(dev), dosage.to(dev), times.to(dev), method=method)
+    h = neural_solve(y0g, *prm, inp["t"].to(dev), dosage.to(dev), times.to(dev), method=method, lanes_per_patient=lanes)
     assert torch.equal(h[0].cpu(), ho[0].detach())
     assert (h.detach().cpu() - ho.detach()).abs().max().item() <= 2e-5 * (1 + ho.abs().max().item())
     (h * cot.to(dev)).sum().backward()

@@ -38,8 +38,8 @@ def test_loss_and_gradients(D, obs, T, B):
 def test_matrix_core_variant_edges(D, obs, T, B):
     """The matrix-core kernel (D = 12 / 48 < obs <= 80, D = 8 / 32 < obs <= 48): partial last output tile, row counts that
     are not a multiple of 16, general (non 0/1) masks, the loss-only launch, and agreement with the lane-per-4-outputs
-    kernel (HODE_READOUT_VALU) on the same inputs."""
-    import os
+    kernel (variant = READOUT_VARIANT_VALU) on the same inputs."""
+    from hode import _lib as L
     from hode.readout import masked_sse_readout
     dev = _dev()
     gen = torch.Generator().manual_seed(obs + B)
@@ -52,21 +52,17 @@ def test_matrix_core_variant_edges(D, obs, T, B):
     ref = torch.sum((x.double() - (hr @ w64.t() + b64)) ** 2 * m.double()) / B
     ref.backward()
 
-    def run():
+    def run(variant=0):
         hg = h.to(dev).requires_grad_(True)
         wg, bg = lin.weight.detach().to(dev).requires_grad_(True), lin.bias.detach().to(dev).requires_grad_(True)
-        lik = masked_sse_readout(hg, x.to(dev), m.to(dev), wg, bg)
+        lik = masked_sse_readout(hg, x.to(dev), m.to(dev), wg, bg, variant=variant)
         lik.backward()
         with torch.no_grad():
-            lik0 = masked_sse_readout(hg.detach(), x.to(dev), m.to(dev), wg.detach(), bg.detach())
+            lik0 = masked_sse_readout(hg.detach(), x.to(dev), m.to(dev), wg.detach(), bg.detach(), variant=variant)
         return lik.item(), lik0.item(), hg.grad.cpu().double(), wg.grad.cpu().double(), bg.grad.cpu().double()
 
     got = run()
-    os.environ["HODE_READOUT_VALU"] = "1"
-    try:
-        alt = run()
-    finally:
-        del os.environ["HODE_READOUT_VALU"]
+    alt = run(L.READOUT_VARIANT_VALU)
     for res in (got, alt):
         assert abs(res[0] - ref.item()) <= 2e-5 * abs(ref.item())
         assert abs(res[1] - ref.item()) <= 2e-5 * abs(ref.item())

@@ -31,15 +31,12 @@ def _flat(f):
 @pytest.mark.parametrize("layout", ["matrix-cores", "lane-per-patient"])
 @pytest.mark.parametrize("D,H", [(20, 43), (4, 9), (20, 17), (20, 64)])
 @pytest.mark.parametrize("method,perturb", [("midpoint", True), ("rk4", True), ("euler", False)])
-def test_real_forward_backward_vs_oracle(D, H, method, perturb, layout, monkeypatch):
+def test_real_forward_backward_vs_oracle(D, H, method, perturb, layout):
     """Both kernel families behind HODE_RHS_ROCHE_REAL: hode_real_mf.hip (default at D = 20; hidden 17 / 43 / 64 exercise
-    2, 3 and 4 hidden tiles) and hode_real.hip (HODE_REAL_LAYOUT=t; always for D = 4)."""
+    2, 3 and 4 hidden tiles) and hode_real.hip (lanes_per_patient=1; always for D = 4)."""
     from hode.real import real_solve
     dev = _dev()
-    if layout == "lane-per-patient":
-        monkeypatch.setenv("HODE_REAL_LAYOUT", "t")
-    else:
-        monkeypatch.delenv("HODE_REAL_LAYOUT", raising=False)
+    lanes = 1 if layout == "lane-per-patient" else 0
     B, Ta, t0 = 37, 30, 8
     gen = torch.Generator().manual_seed(D + H)
     torch.manual_seed(D)
@@ -55,7 +52,7 @@ def test_real_forward_backward_vs_oracle(D, H, method, perturb, layout, monkeypa
     wflat = torch.cat([p.detach().reshape(-1) for p in ps]).to(dev).requires_grad_(True)
     theta = torch.stack([f.k_immunity, f.kel, f.kel2]).detach().to(dev).requires_grad_(True)
     y0g = y0.detach().to(dev).requires_grad_(True)
-    h = real_solve(y0g, theta, wflat, t.to(dev), a[..., 0].to(dev), H, method=method, perturb=perturb)
+    h = real_solve(y0g, theta, wflat, t.to(dev), a[..., 0].to(dev), H, method=method, perturb=perturb, lanes_per_patient=lanes)
     assert (h.detach().cpu() - ho.detach()).abs().max().item() <= 2e-5 * (1 + ho.abs().max().item())
     (h * cot.to(dev)).sum().backward()
     assert _rel(y0g.grad, y0.grad) <= 1e-4

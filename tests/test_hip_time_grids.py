@@ -29,11 +29,10 @@ def _err_h(h, ref):
 
 # ---------------------------------------------------------------------------------------------------- Roche fixed grid
 @pytest.mark.parametrize("case", tg.family("roche"), ids=tg.case_id)
-def test_roche_time_grid(case, monkeypatch, record_property):
+def test_roche_time_grid(case, record_property):
     """rk_* (lanes 1 / 4), split_* (lanes 48 / 0) and mf_* (lanes 16) on the ragged and offset grids, doses on nodes, inside
     steps and before t[0]; need_theta=False against need_theta=True and, on the split layout, tape against no tape as
     test_roche_fixed_grid and test_hip_rk hold them."""
-    monkeypatch.delenv("HODE_RK_LAYOUT", raising=False)
     dev = _dev()
     D, method, ablate, lanes = case["D"], case["method"], case["ablate"], case["lanes"]
     p, ref = tg.roche_inputs(case), tg.roche_ref(case)
@@ -65,17 +64,14 @@ def test_roche_time_grid(case, monkeypatch, record_property):
 
 # ------------------------------------------------------------------------------------------------- NeuralODE fixed grid
 @pytest.mark.parametrize("case", tg.family("neural"), ids=tg.case_id)
-def test_neural_time_grid(case, monkeypatch, record_property):
+def test_neural_time_grid(case, record_property):
     dev = _dev()
-    if case["layout"] == "lane":
-        monkeypatch.setenv("HODE_NEURAL_LAYOUT", "t")
-    else:
-        monkeypatch.delenv("HODE_NEURAL_LAYOUT", raising=False)
     method, perturb = case["method"], case["perturb"]
     p = tg.neural_inputs(case)
     ref = tg.neural_solve_cpu(p, method, perturb)
     tape = not case["onchip"] and case["layout"] == "mf"
-    got = _neural_gpu_tape_backward(p, method, perturb, dev) if tape else _neural_gpu(p, method, perturb, dev)
+    got = _neural_gpu_tape_backward(p, method, perturb, dev) if tape \
+        else _neural_gpu(p, method, perturb, dev, kv.neural_lanes(case))
     assert torch.equal(got["h"][0].cpu(), p["y0"])
     record_property("err_h", _err_h(got["h"], ref["h"]))
     _traj_ok(got["h"], ref["h"])
@@ -180,10 +176,9 @@ def test_neural_dopri5_time_grid(case, record_property):
 
 # ------------------------------------------------------------------------------------------------------ real-data Roche
 @pytest.mark.parametrize("case", tg.family("real"), ids=tg.case_id)
-def test_real_time_grid(case, monkeypatch, record_property):
+def test_real_time_grid(case, record_property):
     """real_kernel and real_mf_kernel (on-chip and tape-writing backward): the dose row is floor(t), on grids whose nodes lie
     on both sides of integer times and, from t[0] = 2.5, past the last action row."""
-    monkeypatch.delenv("HODE_REAL_LAYOUT", raising=False)
     dev = _dev()
     H, method = case["H"], case["method"]
     p, ref = tg.real_problem(case)

@@ -397,13 +397,13 @@ def test_new_families_are_covered_by_substantive_cases(compiled):
 
 
 def test_neural_rules():
-    assert kv.neural_layout(6, "t") == "lane" and kv.neural_layout(6, "tape") == "lane" and kv.neural_layout(6, "m") == "mf"
-    assert kv.neural_layout(14) == "mf" and kv.neural_layout(4, "") == "mf"
+    assert kv.neural_layout(6, 1) == "lane" and kv.neural_layout(12, 1) == "lane" and kv.neural_layout(6, 16) == "mf"
+    assert kv.neural_layout(14) == "mf" and kv.neural_layout(4, 0) == "mf"
     with pytest.raises(AssertionError):
-        kv.neural_layout(14, "t")
+        kv.neural_layout(14, 1)
     assert kv.neural_grid(65, "mf") == 5 and kv.neural_grid(65, "lane") == 2 and kv.neural_grid(64, "lane") == 1
-    assert kv.neural_fixed(8, kv.RK4, None, False)[-1] == "hode::neural_mf_bwd_kernel<8, 2, false>"
-    assert "hode::transpose_w2_kernel" in kv.neural_fixed(8, kv.RK4, "t", True)
+    assert kv.neural_fixed(8, kv.RK4, 0, False)[-1] == "hode::neural_mf_bwd_kernel<8, 2, false>"
+    assert "hode::transpose_w2_kernel" in kv.neural_fixed(8, kv.RK4, 1, True)
     assert not any("initbwd" in n for n in kv.neural_dopri5_kernels(8, 0, False))
     assert not any("initbwd" in n for n in kv.neural_dopri5_kernels(8, 5, True))
     # the dose / tile edges the issue names appear somewhere in the table
@@ -419,7 +419,9 @@ def test_neural_rules():
 def test_neural_source_pins_the_restated_rules():
     """The lines kv.neural_layout / neural_fixed / neural_dopri5_kernels restate, as they read in the source."""
     nh = _norm(_strip_and_expand(open(os.path.join(CSRC, "hode_neural.hip")).read()))
-    assert "if (!(env && env[0] == 't')) return launch_neural_mf(d, a, bwd, s);" in nh
+    assert "bool neural_lanes(const hode_solve_desc* d) { return d->lanes_per_patient == 1; }" in nh
+    assert "if (!neural_lanes(d)) return launch_neural_mf(d, a, bwd, s);" in nh
+    assert "bool neural_onchip(const hode_solve_desc* d) { return !neural_lanes(d) && d->grad_w1 != nullptr; }" in nh
     assert "if (D != 6 && D != 8 && D != 12)" in nh
     assert "const dim3 grid((d->batch + 63) / 64), block(64);" in nh
     mf = _norm(_strip_and_expand(open(os.path.join(CSRC, "hode_neural_mf.hip")).read()))
@@ -464,24 +466,25 @@ def test_lstm_source_pins_the_restated_rules():
     lh = _norm(_strip_and_expand(open(os.path.join(CSRC, "hode_lstm.hip")).read()))
     assert "static const int kSizes[] = {%s};" % ", ".join(str(v) for v in kv.LSTM_SIZES) in lh
     assert "const bool vec4 = (obs & 3) == 0 &&" in lh
+    assert "if (d->patient_tiles >= 1 && d->patient_tiles <= (bwd_compatible ? 3 : 4)) G->NT = d->patient_tiles;" in lh
     import build_hip
     assert tuple(sorted(build_hip.LSTM_TPWS)) == tuple(sorted(kv.LSTM_TPWS))
 
 
-def _lstm_desc(T, B, obs, H, tape):
+def _lstm_desc(T, B, obs, H, tape, patient_tiles=0):
     from hode import _lib as L
     d = L.new_lstm_desc()
     d.seq_len, d.batch, d.input_dim, d.hidden_dim, d.obs_dim, d.save_tape = T, B, obs + 1, H, obs, int(tape)
+    d.patient_tiles = patient_tiles
     return d
 
 
-def test_lstm_geometry_matches_the_workspace_size(monkeypatch):
+def test_lstm_geometry_matches_the_workspace_size():
     """hode_lstm_workspace_bytes against kv.lstm_workspace_bytes: the packed weights depend on Hp and KQ4, the tape on NT
     (nblk NT differs between tiles for ragged batches) -- with NT chosen by the batch size (both sides of every tie) and
-    forced by HODE_LSTM_NT, the staging clamp included."""
+    forced by the descriptor's patient_tiles, the staging clamp included."""
     import hode
     lib = hode.lib()
-    monkeypatch.delenv("HODE_LSTM_NT", raising=False)
     Bs = (1, 17, 4095, 4096, 4097, 6145, 8192, 8193, 12288, 12289, 16385, 20481, 24577)
     n = 0
     for H in (1, 13, 16, 17, 47, 64, 65, 96, 97, 125, 128, 129, 160):
@@ -493,31 +496,27 @@ def test_lstm_geometry_matches_the_workspace_size(monkeypatch):
                     n += 1
     assert n > 1000
     for nt in (1, 2, 3, 4):
-        monkeypatch.setenv("HODE_LSTM_NT", str(nt))
         for B in (37, 101, 4097):
             for obs in (20, 100):
-                got = lib.hode_lstm_workspace_bytes(_lstm_desc(2, B, obs, 40, True))
+                got = lib.hode_lstm_workspace_bytes(_lstm_desc(2, B, obs, 40, True, nt))
                 assert got == kv.lstm_workspace_bytes(2, B, obs + 1, 40, obs, True, nt), (nt, B, obs)
 
 
-def test_readout_rules_match_the_workspace_size(monkeypatch):
+def test_readout_rules_match_the_workspace_size():
     """hode_readout_workspace_bytes = readout_waves * (1 + obs D + obs) floats: the waves depend on whether readout_mf was
     chosen (16 rows per wave-iteration against 64 / (obs / 4)) -- every obs at both latent dimensions with a window, with and
-    without HODE_READOUT_VALU."""
+    without the descriptor's variant set to READOUT_VARIANT_VALU."""
     import hode
     from hode import _lib as L
     lib = hode.lib()
-    for valu in (False, True):
-        if valu:
-            monkeypatch.setenv("HODE_READOUT_VALU", "1")
-        else:
-            monkeypatch.delenv("HODE_READOUT_VALU", raising=False)
+    assert kv.READOUT_VARIANT_VALU == L.READOUT_VARIANT_VALU
+    for valu in (0, L.READOUT_VARIANT_VALU):
         for D in (4, 6, 8, 12):
             for obs in range(4, 129, 4):
                 for rows in (1, 37, 1000, 40000):
                     d = L.ReadoutDesc()
                     d.struct_size = ctypes.sizeof(L.ReadoutDesc)
-                    d.latent_dim, d.obs_dim, d.rows = D, obs, rows
+                    d.latent_dim, d.obs_dim, d.rows, d.variant = D, obs, rows, valu
                     want = kv.readout_waves(rows, obs, D, valu) * (1 + obs * D + obs) * 4
                     assert lib.hode_readout_workspace_bytes(d) == want, (valu, D, obs, rows)
     assert [o for o in range(4, 129, 4) if kv.readout_mf(12, o)] == [52, 56, 60, 64, 68, 72, 76, 80]
@@ -528,7 +527,7 @@ def test_readout_rules_match_the_workspace_size(monkeypatch):
     assert "if (d->latent_dim == 20) HODE_RM(20) else HODE_RM(4)" in open(os.path.join(CSRC, "hode_readout_mlp.hip")).read()
 
 
-def test_neural_rule_matches_the_workspace_size(monkeypatch):
+def test_neural_rule_matches_the_workspace_size():
     """hode_workspace_bytes(..., WS_RK_BWD) of the neural rhs: with grad_w1 (the on-chip backward) one block of
     2 HT 256 + 16 floats of partials per 16-patient wave (HT = ceil(10 D / 16)), independent of T and the method; without
     grad_w1, or with the lane layout, the four tapes (T - 1) stages (10 D + 10 D + D + 1 + D) B floats."""
@@ -538,18 +537,15 @@ def test_neural_rule_matches_the_workspace_size(monkeypatch):
     buf = (ctypes.c_float * 4)()
     al = lambda x: (x + 255) // 256 * 256  # noqa: E731
 
-    def size(D, B, T, method, onchip):
+    def size(D, B, T, method, onchip, lanes):
         d = L.new_solve_desc()
         d.rhs_kind, d.method, d.batch, d.latent_dim, d.n_times, d.hidden_dim = L.RHS_NEURAL, L.METHODS[method], B, D, T, 10 * D
+        d.lanes_per_patient = lanes
         if onchip:
             d.grad_w1 = ctypes.addressof(buf)  # never dereferenced: only selects the on-chip layout
         return lib.hode_workspace_bytes(d, L.WS_RK_BWD)
 
-    for env in (None, "t"):
-        if env:
-            monkeypatch.setenv("HODE_NEURAL_LAYOUT", env)
-        else:
-            monkeypatch.delenv("HODE_NEURAL_LAYOUT", raising=False)
+    for lanes in (0, 1):
         for D in (4, 6, 8, 10, 12, 14):
             HD, HT = 10 * D, (10 * D + 15) // 16
             for B in (1, 16, 17, 64, 65, 129):
@@ -560,5 +556,5 @@ def test_neural_rule_matches_the_workspace_size(monkeypatch):
                         tapes = w2t + al(inst * HD * B * 4) * 2 + al(inst * (D + 1) * B * 4) + al(inst * D * B * 4)
                         onchip = w2t + al(kv.neural_grid(B, "mf") * (2 * HT * 256 + 16) * 4)
                         for oc in (True, False):
-                            want = onchip if oc and not env else tapes
-                            assert size(D, B, T, method, oc) == want, (env, D, B, T, method, oc)
+                            want = onchip if oc and not lanes else tapes
+                            assert size(D, B, T, method, oc, lanes) == want, (lanes, D, B, T, method, oc)

@@ -238,7 +238,7 @@ def kernels(case):
         return kv.roche_fixed(case["D"], case["lanes"], kv.METHODS[case["method"]], case["ablate"], case["need_theta"],
                               case["tape"], case["T"], kv.ROCHE_N)
     if f == "neural":
-        return kv.neural_fixed(case["D"], kv.METHODS[case["method"]], "t" if case["layout"] == "lane" else None, case["onchip"])
+        return kv.neural_fixed(case["D"], kv.METHODS[case["method"]], kv.neural_lanes(case), case["onchip"])
     if f == "dopri5":
         return kv.dopri5_kernels(case["D"], case["lanes"], case["ablate"], case["need_theta"], case["detach"], kv.DOPRI5_N)
     if f == "neural_dopri5":
