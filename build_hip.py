@@ -3,7 +3,9 @@
 
 LIBRARIES is the table of what is built: libhode.so (C ABI include/hode.h) and the single-unit side libraries
 libhode_flow.so, libhode_mix.so and libhode_blend.so, each with a C ABI header of its own so that its kernels stay out of
-libhode.so; DATA_LIBRARIES holds libhode_datagen.so in the same rows.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
+libhode.so; DATA_LIBRARIES holds libhode_datagen.so in the same rows, and TEST_LIBRARIES libhode_probe.so (C ABI
+include/hode_probe.h), which runs the shared device helpers on their own for tests/test_hip_helpers.py and which nothing
+under hode/ loads.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
 depfile, its flags or this script changed), links each library whose objects are newer than it, and writes
 digest(<library>) next to it as <library>.so.digest; tests and hode/_loader.py compare that stamp with the tree."""
 import argparse
@@ -76,14 +78,24 @@ LIBRARIES = {lib.name: lib for lib in (
 DATA_LIBRARIES = {lib.name: lib for lib in (
     _side("datagen"),                               # the synthetic data generator (DataGeneratorRoche)
 )}
+#: test-only libraries, same rows: the probe of the device helpers, compiled with the product FLAGS.  `extra` lists every
+#: header of csrc/ the unit includes, so that its digest follows an edit of a helper.
+TEST_LIBRARIES = {lib.name: lib for lib in (
+    _side("probe", *(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_lanes.hpp", "hode_lstm_kernels.hpp",
+                                                  "hode_neural_mf.hpp", "hode_neural_args.hpp", "hode_roche.hpp",
+                                                  "hode_host.hpp")), "include/hode.h"),
+)}
 
 
 def _library(name):
-    return LIBRARIES[name] if name in LIBRARIES else DATA_LIBRARIES[name]
+    for table in (LIBRARIES, DATA_LIBRARIES, TEST_LIBRARIES):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 
 def all_libraries():
-    return list(LIBRARIES.values()) + list(DATA_LIBRARIES.values())
+    return list(LIBRARIES.values()) + list(DATA_LIBRARIES.values()) + list(TEST_LIBRARIES.values())
 
 
 OUT = LIBRARIES["libhode.so"].out

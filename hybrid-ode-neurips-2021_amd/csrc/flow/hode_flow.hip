@@ -20,7 +20,7 @@
 
 namespace hode_flow {
 
-using hode::exp_f32;
+using hode::exp_full_f32;
 using hode::log_f32;
 using hode::tanh_precise_f32;
 
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void flow_fwd_kernel(FlowArgs a) {
     for (int d = 0; d < DT; ++d) {
       const float lv = d < a.D ? a.log_var[(size_t)bb * a.D + d] : 0.f;
       mu[d] = d < a.D ? a.mu[(size_t)bb * a.D + d] : 0.f;
-      sg[d] = exp_f32(0.5f * lv);
+      sg[d] = exp_full_f32(0.5f * lv);
       if (d < a.D) gauss_const -= 0.5f * lv + kLogSqrt2Pi;
     }
     for (int s = slot; s < a.S; s += L) {
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(kBlock) void flow_fwd_kernel(FlowArgs a) {
       for (int d = 0; d < DT; ++d) {
         if (d < a.D) {
           const float y = z[d] - 5.0f;
-          const float zo = exp_f32(y);
+          const float zo = exp_full_f32(y);
           logdet += y;
           log_p += kLogRate - kRate * zo;
           if (a.z_out) a.z_out[row + d] = zo;
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(kBlock) void flow_bwd_kernel(FlowArgs a) {
 #pragma unroll
   for (int d = 0; d < DT; ++d) {
     mu[d] = active && d < a.D ? a.mu[(size_t)bb * a.D + d] : 0.f;
-    sg[d] = exp_f32(0.5f * (active && d < a.D ? a.log_var[(size_t)bb * a.D + d] : 0.f));
+    sg[d] = exp_full_f32(0.5f * (active && d < a.D ? a.log_var[(size_t)bb * a.D + d] : 0.f));
     acc_mu[d] = 0.f;
     acc_e[d] = 0.f;
   }
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(kBlock) void flow_bwd_kernel(FlowArgs a) {
 #pragma unroll
     for (int d = 0; d < DT; ++d) {
       const float gz = (a.gz && valid && d < a.D) ? a.gz[row + d] : 0.f;
-      zb[d] = (valid && d < a.D) ? __builtin_fmaf(exp_f32(z[d] - 5.0f), __builtin_fmaf(kRate, c, gz), -c) : 0.f;
+      zb[d] = (valid && d < a.D) ? __builtin_fmaf(exp_full_f32(z[d] - 5.0f), __builtin_fmaf(kRate, c, gz), -c) : 0.f;
     }
 #pragma unroll
     for (int k = kMaxK - 1; k >= 0; --k) {

@@ -53,7 +53,9 @@ HODE_DEV void lds_barrier() {
 }
 
 HODE_DEV float sigmoid_gate(float x) {
-  // 1 / (1 + exp(-x)) on v_exp + v_rcp (<= 2 ulp); exp overflow -> rcp(inf) = 0, underflow -> 1
+  // 1 / (1 + exp(-x)) on v_exp + v_rcp.  ABSOLUTE error: bound 1.9e-7, measured 1.0e-7 (tests/test_hip_helpers.py); in ulp
+  // the error grows with |x| for x < 0 (the fp32 log2(e) and the rounded product: bound (5 + 1.23 |x|) ulp; measured 2.24 ulp
+  // for |x| < 1, 9.04 ulp for |x| < 8, 61.9 ulp up to 87.3).  exp overflow -> rcp(inf) = 0, underflow -> 1; a result below 2^-126 is flushed to 0.
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
 }
 

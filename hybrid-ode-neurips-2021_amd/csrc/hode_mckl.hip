@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void mc_kl_exp_kernel(McKlArgs a) {
   const long long i = blockIdx.x * 256LL + threadIdx.x;
   if (i >= a.rows) return;
   const float mu = a.mu[i], lv = a.log_var[i];
-  const float sigma = exp_f32(0.5f * lv);
+  const float sigma = exp_full_f32(0.5f * lv);
   const float inv_var = __builtin_amdgcn_rcpf(sigma * sigma);
   const float e = a.eps_clamp;
   // clamped-sample constants

@@ -10,8 +10,6 @@
 
 namespace hode {
 
-typedef float v4 __attribute__((ext_vector_type(4)));
-
 template <int D>
 struct NeuralMf {
   static constexpr int HD = 10 * D;

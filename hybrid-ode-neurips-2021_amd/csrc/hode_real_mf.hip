@@ -23,19 +23,10 @@
 
 namespace hode {
 
-typedef float v4 __attribute__((ext_vector_type(4)));
-
 HODE_DEV v4 mfma4(float a, float b, v4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 constexpr float kTanhScale = 2.885390081777927f;   // 2 log2(e)
-// tanh(z) = 1 - 2 / (exp2(z') + 1) for z' = kTanhScale z, four values
-HODE_DEV v4 tanh_scaled4(const v4& z) {
-  const f2 e0 = pair2(__builtin_amdgcn_exp2f(z[0]), __builtin_amdgcn_exp2f(z[1])) + splat2(1.0f);
-  const f2 e1 = pair2(__builtin_amdgcn_exp2f(z[2]), __builtin_amdgcn_exp2f(z[3])) + splat2(1.0f);
-  const f2 t0 = __builtin_elementwise_fma(pair2(__builtin_amdgcn_rcpf(e0.x), __builtin_amdgcn_rcpf(e0.y)), splat2(-2.0f), splat2(1.0f));
-  const f2 t1 = __builtin_elementwise_fma(pair2(__builtin_amdgcn_rcpf(e1.x), __builtin_amdgcn_rcpf(e1.y)), splat2(-2.0f), splat2(1.0f));
-  return v4{t0.x, t0.y, t1.x, t1.y};
-}
+// the activations are tanh_scaled4 (hode_common.hpp) of z' = kTanhScale z
 
 template <int HT>
 struct RealMf {

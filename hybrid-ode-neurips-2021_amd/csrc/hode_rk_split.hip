@@ -208,14 +208,7 @@ struct MlRows {
     }
     return Y;
   }
-  static HODE_DEV Own tanh_scaled(Own z) {  // z already carries the factor 2 log2(e)
-    if constexpr (MR == 2) {
-      const f2 e = pair2(__builtin_amdgcn_exp2f(z.x), __builtin_amdgcn_exp2f(z.y)) + splat2(1.0f);
-      return vfma(pair2(__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)), splat2(-2.0f), splat2(1.0f));
-    } else {
-      return __builtin_fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(z) + 1.0f), -2.0f, 1.0f);
-    }
-  }
+  // the activation is tanh_scaled (hode_common.hpp): the weights already carry the factor 2 log2(e)
   HODE_DEV Own rhs(const Stage& Y) const {
     if constexpr (MR == 2) {
       // two interleaved accumulators: the result of a packed op cannot be consumed by the very next instruction (the

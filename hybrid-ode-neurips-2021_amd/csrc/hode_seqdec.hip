@@ -29,8 +29,6 @@
 namespace hode {
 namespace {
 
-typedef float v4 __attribute__((ext_vector_type(4)));
-
 struct SeqArgs {
   const int* __restrict__ idx;    // [T] action row of step k
   const float* __restrict__ tau;  // [T] time feature of step k
@@ -49,12 +47,6 @@ struct SeqArgs {
 };
 
 HODE_DEV v4 zero4() { return v4{0.f, 0.f, 0.f, 0.f}; }
-HODE_DEV f2 lo2(const v4& v) { return pair2(v[0], v[1]); }
-HODE_DEV f2 hi2(const v4& v) { return pair2(v[2], v[3]); }
-HODE_DEV v4 cat4(f2 a, f2 b) { return v4{a.x, a.y, b.x, b.y}; }
-HODE_DEV f2 sigmoid2(f2 x) { return vfma(tanh_f32(x * splat2(0.5f)), splat2(0.5f), splat2(0.5f)); }  // 0.5 + 0.5 tanh(x/2)
-HODE_DEV v4 sigmoid4(const v4& x) { return cat4(sigmoid2(lo2(x)), sigmoid2(hi2(x))); }
-HODE_DEV v4 tanh4(const v4& x) { return cat4(tanh_f32(lo2(x)), tanh_f32(hi2(x))); }
 
 // rows 16 j + 4 g + r < D of one patient's row vector; the rest 0
 HODE_DEV v4 load_tile(const float* __restrict__ src, int j, int g, int D) {
