@@ -5,7 +5,8 @@ LIBRARIES is the table of what is built: libhode.so (C ABI include/hode.h) and t
 libhode_flow.so, libhode_mix.so and libhode_blend.so, each with a C ABI header of its own so that its kernels stay out of
 libhode.so; DATA_LIBRARIES holds libhode_datagen.so in the same rows, and TEST_LIBRARIES libhode_probe.so (C ABI
 include/hode_probe.h), which runs the shared device helpers on their own for tests/test_hip_helpers.py and which nothing
-under hode/ loads.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
+under hode/ loads; SOLVER_LIBRARIES libhode_neural_odd.so (C ABI include/hode_neural_odd.h), the NeuralODE kernels of
+libhode.so instantiated at the odd latent dimensions 5 .. 15, one unit per dimension.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
 depfile, its flags or this script changed), links each library whose objects are newer than it, and writes
 digest(<library>) next to it as <library>.so.digest; tests and hode/_loader.py compare that stamp with the tree."""
 import argparse
@@ -24,6 +25,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
          "-Wno-unused-but-set-variable"]
 RK_DIMS = (4, 6, 8, 12, 20)
 DP_DIMS = (4, 6, 8, 12)
+NEURAL_ODD_DIMS = (5, 7, 9, 11, 13, 15)  # csrc/neural_odd/hode_neural_odd_dim.hip; the even ones are in libhode.so
 LSTM_TPWS = (1, 2, 3, 4, 5, 6, 8, 10)   # padded hidden sizes 16 * TPW (csrc/hode_lstm_tpw.hip)
 # per-unit flags (measured on MI355X)
 # -fno-slp-vectorize on the split kernels: packed-fp32 pairing costs more v_mov than it saves (step 0.228 -> 0.207 ms)
@@ -87,15 +89,33 @@ TEST_LIBRARIES = {lib.name: lib for lib in (
 )}
 
 
+def _neural_odd_units():
+    d = os.path.join(CSRC, "neural_odd")
+    return [("hode_neural_odd", os.path.join(d, "hode_neural_odd.hip"), [])] + \
+        [("hode_neural_odd_d%d" % n, os.path.join(d, "hode_neural_odd_dim.hip"), ["-DHODE_DIM=%d" % n]) for n in NEURAL_ODD_DIMS]
+
+
+#: solver libraries next to libhode.so, same rows: kernels of libhode.so's templates at sizes libhode.so does not hold.
+#: `extra` lists every header of csrc/ the units include, so that the digest follows them.
+SOLVER_LIBRARIES = {lib.name: lib for lib in (
+    Library("libhode_neural_odd.so", PKG + "/csrc/neural_odd", "include/hode_neural_odd.h",
+            tuple(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_lanes.hpp", "hode_roche.hpp", "hode_host.hpp",
+                                               "hode_dopri5_kernels.hpp", "hode_neural_args.hpp", "hode_neural_mf.hpp",
+                                               "hode_neural_mf_kernels.hpp", "hode_neural_dopri5_kernels.hpp"))
+            + ("include/hode.h",), _neural_odd_units),
+)}
+
+
 def _library(name):
-    for table in (LIBRARIES, DATA_LIBRARIES, TEST_LIBRARIES):
+    for table in (LIBRARIES, DATA_LIBRARIES, TEST_LIBRARIES, SOLVER_LIBRARIES):
         if name in table:
             return table[name]
     raise KeyError(name)
 
 
 def all_libraries():
-    return list(LIBRARIES.values()) + list(DATA_LIBRARIES.values()) + list(TEST_LIBRARIES.values())
+    return (list(LIBRARIES.values()) + list(DATA_LIBRARIES.values()) + list(TEST_LIBRARIES.values())
+            + list(SOLVER_LIBRARIES.values()))
 
 
 OUT = LIBRARIES["libhode.so"].out

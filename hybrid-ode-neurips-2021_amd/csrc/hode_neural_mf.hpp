@@ -156,6 +156,9 @@ HODE_DEV v4 vfma4(const v4& a, const v4& b, const v4& c) {
 // contraction index; the outer products contract over PATIENTS, so the four operands go through LDS patient-major
 // (16-byte stores: a lane's four rows are consecutive) and come back with lane (m, kk) reading image[4c + kk][.. + m]:
 // A[m][kk] / B[kk][m] fragments of patient chunk c.  72 ds_read_b32 + 18 ds_write_b128 + 64 MFMAs per stage.
+// D = 15: [y, Dose] fills the 16-row tile, there is no row for the ones (kOnesRow false).  db1 then is accumulated like db2:
+// a per-lane running sum of u1 per hidden tile, summed over the wave's 16 patients at store() into 16 HT floats of their
+// own behind db2 in the partial block.
 template <int D>
 struct NeuralGradAcc {
   static constexpr int HT = NeuralMf<D>::HT;
@@ -164,9 +167,12 @@ struct NeuralGradAcc {
   static constexpr int PH = ((16 * HT - 16 + 63) / 64) * 64 + 16;
   static constexpr int PS = 16;
   static constexpr int kLdsFloats = 16 * (2 * PH + 2 * PS);
-  static constexpr int NP = 2 * HT * 256 + 16;  // floats per wave in the partial array
+  static constexpr bool kOnesRow = D + 2 <= 16;
+  static constexpr int NB1 = kOnesRow ? 0 : 16 * HT;  // db1 slots of the partial block when dW1 has no column for it
+  static constexpr int NP = 2 * HT * 256 + 16 + NB1;  // floats per wave in the partial array
   static constexpr int GB = (D + 1) / 4, RB = (D + 1) % 4;  // tile position of the ones row behind [y, Dose]
   v4 dW1[HT], dW2[HT], db2;
+  v4 db1[kOnesRow ? 1 : HT];  // used without the ones row only
   float *U1, *A1, *E, *U2;
 
   HODE_DEV void init(float* lds) {
@@ -177,9 +183,15 @@ struct NeuralGradAcc {
 #pragma unroll
     for (int i = 0; i < HT; ++i) dW1[i] = dW2[i] = splat4(0.f);
     db2 = splat4(0.f);
+    if constexpr (D + 2 > 16) {
+#pragma unroll
+      for (int i = 0; i < HT; ++i) db1[i] = splat4(0.f);
+    }
   }
   HODE_DEV void add(const v4 (&u1)[HT], v4 e, const v4& u2, const v4 (&a1)[HT], int g, int n) {
-    if (g == GB) e[RB] = 1.0f;
+    if constexpr (kOnesRow) {
+      if (g == GB) e[RB] = 1.0f;
+    }
     __syncthreads();  // the previous call's reads are done
 #pragma unroll
     for (int i = 0; i < HT; ++i) {
@@ -207,8 +219,12 @@ struct NeuralGradAcc {
       }
     }
     db2 = db2 + u2;
+    if constexpr (D + 2 > 16) {
+#pragma unroll
+      for (int i = 0; i < HT; ++i) db1[i] = db1[i] + u1[i];
+    }
   }
-  // one block of NP floats per wave: [dW1 tiles | dW2 tiles] as [tile][lane][4], then db2[16]
+  // one block of NP floats per wave: [dW1 tiles | dW2 tiles] as [tile][lane][4], then db2[16], then db1[16 HT] (D = 15)
   HODE_DEV void store(float* __restrict__ out, int lane) {
 #pragma unroll
     for (int i = 0; i < HT; ++i) {
@@ -219,6 +235,14 @@ struct NeuralGradAcc {
 #pragma unroll
     for (int r = 0; r < 4; ++r) s[r] = row_sum(db2[r]);  // over the 16 patients of this row group
     if ((lane & 15) == 0) *reinterpret_cast<v4*>(out + 2 * HT * 256 + 4 * (lane >> 4)) = s;
+    if constexpr (D + 2 > 16) {
+#pragma unroll
+      for (int i = 0; i < HT; ++i) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[r] = row_sum(db1[i][r]);  // hidden units 16 i + 4 g + r
+        if ((lane & 15) == 0) *reinterpret_cast<v4*>(out + 2 * HT * 256 + 16 + 16 * i + 4 * (lane >> 4)) = s;
+      }
+    }
   }
   HODE_DEV static void store_zero(float* __restrict__ out, int lane) {
     for (int i = lane; i < NP; i += 64) out[i] = 0.f;
@@ -235,6 +259,13 @@ __global__ __launch_bounds__(64) void neural_grad_fold_kernel(const float* __res
   for (int w = lane; w < n_waves; w += 64) s += partials[(size_t)w * NP + j];
   s = wave_sum(s);
   if (lane != 0) return;
+  if constexpr (D + 2 > 16) {
+    if (j >= 2 * HT * 256 + 16) {  // db1 without the ones row
+      const int hid = j - (2 * HT * 256 + 16);
+      if (hid < HD && gb1) gb1[hid] += s;
+      return;
+    }
+  }
   if (j >= 2 * HT * 256) {
     const int o = j - 2 * HT * 256;
     if (o < D && gb2) gb2[o] += s;

@@ -13,6 +13,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from ._neural_odd_lib import DIMS as NEURAL_ODD_DIMS, neural_solver_library
 from .solver import _f32c, _ptr, _require_gpu, _stream
 
 #: last forward's step statistics (diagnostics; mirrors what torchdiffeq exposes through nfe counters)
@@ -31,7 +32,8 @@ def read_tape():
         raise L.HodeConfigError("hode.adaptive.read_tape: no workspace kept (set keep_workspace = True before the solve)")
     ws, d, n_acc = _last_ws
     off = (C.c_size_t * 5)()
-    L.check(L.lib().hode_dopri5_tape_offsets(d, off), "hode_dopri5_tape_offsets")
+    lib = neural_solver_library(d.latent_dim) if d.rhs_kind == L.RHS_NEURAL else L.lib()
+    L.check(lib.hode_dopri5_tape_offsets(d, off), "hode_dopri5_tape_offsets")
     raw = ws.cpu().numpy()
     import numpy as np
     rec = L.Dopri5InitRecord.from_buffer_copy(raw[off[0]:off[0] + C.sizeof(L.Dopri5InitRecord)].tobytes())
@@ -166,7 +168,7 @@ class _NeuralDopri5(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y0, w1, b1, w2, b2, t, dosage, dose_times, rtol, atol, max_steps, detach_first_step, grad_enabled=True):
         _require_gpu(y0, w1, t, dosage, dose_times)
-        lib = L.lib()
+        lib = neural_solver_library(y0.shape[-1])
         B, D = y0.shape
         T = t.numel()
         y0c, tc, dosc, dtc = _f32c(y0), _f32c(t), _f32c(dosage), _f32c(dose_times)
@@ -216,7 +218,7 @@ class _NeuralDopri5(torch.autograd.Function):
     def backward(ctx, grad_h):
         h, tc, dosc, dtc, y0c, w1c, b1c, w2c, b2c, ws = ctx.saved_tensors
         rtol, atol, steps, n_accepted, detach_first = ctx.meta
-        lib = L.lib()
+        lib = neural_solver_library(h.shape[-1])
         T, B, D = h.shape
         gh = _f32c(grad_h)
         gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)
@@ -242,6 +244,8 @@ class _NeuralDopri5(torch.autograd.Function):
 #: latent dimensions the fused neural dopri5 kernels are compiled for (csrc/hode_neural_dopri5.hip: [y, Dose, 1] must fit
 #: one 16-row MFMA tile); the reference's simulation configs use 6, 8 and 12
 NEURAL_DIMS = (4, 6, 8, 10, 12, 14)
+#: beside them NEURAL_ODD_DIMS = (5, 7, ..., 15): the same kernels in libhode_neural_odd.so ([y, Dose] alone fills the tile
+#: at 15; the layer-1 bias gradient then has a path of its own, csrc/hode_neural_mf.hpp)
 
 
 def neural_dopri5(y0, w1, b1, w2, b2, t, dosage, dose_times, rtol=1e-7, atol=1e-9, max_steps=0, detach_first_step=False):

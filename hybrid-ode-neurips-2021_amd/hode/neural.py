@@ -1,7 +1,9 @@
 """Fixed-grid solve of the pure neural latent ODE (reference ``NeuralODE``, ``model.py:969-1026``) on the gfx950 kernels.
 
 The matrix-core backward kernel returns ``grad_y0`` and accumulates the weight gradients on chip (outer products over the
-wave's patients as MFMAs, one partial block per wave, fixed-order fold).  The one-patient-per-lane kernels
+wave's patients as MFMAs, one partial block per wave, fixed-order fold).  The even latent dimensions 4 .. 14 are served by
+libhode.so, the odd ones 5 .. 15 by libhode_neural_odd.so (``_neural_odd_lib.neural_solver_library``: same kernels, same
+descriptor).  The one-patient-per-lane kernels
 (``lanes_per_patient=1``) tape the operands of those outer products instead and they are contracted here with batched
 BLAS GEMMs."""
 
@@ -12,6 +14,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from ._neural_odd_lib import neural_solver_library
 from .solver import _f32c, _ptr, _require_gpu, _stream
 
 _STAGES = {L.METHOD_EULER: 1, L.METHOD_MIDPOINT: 2, L.METHOD_RK4_38: 4}
@@ -34,7 +37,7 @@ class _NeuralFixedGrid(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y0, w1, b1, w2, b2, t, dosage, dose_times, method, perturb, lanes):
         _require_gpu(y0, w1, t, dosage, dose_times)
-        lib = L.lib()
+        lib = neural_solver_library(y0.shape[-1])
         y0c, tc, dosc, dtc = _f32c(y0), _f32c(t), _f32c(dosage), _f32c(dose_times)
         w1c, b1c, w2c, b2c = _f32c(w1), _f32c(b1), _f32c(w2), _f32c(b2)
         B, D = y0c.shape
@@ -54,7 +57,7 @@ class _NeuralFixedGrid(torch.autograd.Function):
     def backward(ctx, grad_h):
         h, tc, dosc, dtc, w1c, b1c, w2c, b2c = ctx.saved_tensors
         method, perturb, lanes = ctx.meta
-        lib = L.lib()
+        lib = neural_solver_library(h.shape[-1])
         T, B, D = h.shape
         gh = _f32c(grad_h)
         gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)

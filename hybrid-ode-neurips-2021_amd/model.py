@@ -354,10 +354,12 @@ class NeuralODE(nn.Module):
         from hode import neural
         if method == "dopri5":
             from hode import adaptive
-            if self.latent_dim not in adaptive.NEURAL_DIMS:
-                raise hode.HodeConfigError("hode: NeuralODE with method='dopri5' is compiled for latent dimensions %s (got %d); "
+            if self.latent_dim not in adaptive.NEURAL_DIMS and self.latent_dim not in adaptive.NEURAL_ODD_DIMS:
+                raise hode.HodeConfigError("hode: NeuralODE with method='dopri5' is compiled for latent dimensions %s "
+                                           "(libhode.so) and %s (libhode_neural_odd.so) (got %d); "
                                            "there is no torch-eager path in the product"
-                                           % (", ".join(str(d) for d in adaptive.NEURAL_DIMS), self.latent_dim))
+                                           % (", ".join(str(d) for d in adaptive.NEURAL_DIMS),
+                                              ", ".join(str(d) for d in adaptive.NEURAL_ODD_DIMS), self.latent_dim))
             # the reference's default for --method=neural (sim_config.py:50): fused MFMA attempt kernels
             return adaptive.neural_dopri5(y0, self.ml_net[0].weight, self.ml_net[0].bias, self.ml_net[2].weight,
                                           self.ml_net[2].bias, t, self.dosage, self.times, rtol=rtol, atol=atol)

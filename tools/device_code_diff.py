@@ -1,7 +1,8 @@
 """Is the device code of two built trees the same?  python tools/device_code_diff.py <tree A> <tree B>
 
 For every object under csrc/**/build/ of both trees (experiment objects `<unit>__<tag>.o` aside): the .text bytes of its
-gfx950 code object and every kernel descriptor.  Prints one row per unit and exits 1 on any difference.  Symbol names are
+gfx950 code object and every kernel descriptor.  Prints one row per unit and exits 1 on any difference or a unit that only
+tree A has; a unit that only tree B has is listed as added.  Symbol names are
 not compared (the compilation-unit id in them follows the source path)."""
 import glob, hashlib, os, subprocess, sys, tempfile
 
@@ -29,14 +30,18 @@ def text_bytes(obj):
 
 if __name__ == "__main__":
     a, b = objects(sys.argv[1]), objects(sys.argv[2])
-    bad = sorted(set(a) ^ set(b))
-    print("%-28s %10s %8s  %-12s %s" % ("unit", ".text B", "kernels", ".text sha256", "result"))
+    bad = sorted(set(a) - set(b))   # a unit that is gone; units only tree B has are listed as added
+    print("%-40s %10s %8s  %-12s %s" % ("unit", ".text B", "kernels", ".text sha256", "result"))
     for unit in sorted(set(a) & set(b)):
         ta, tb = text_bytes(a[unit]), text_bytes(b[unit])
         ka, kb = sorted(kernel_descriptors(a[unit])), sorted(kernel_descriptors(b[unit]))
         same = ta == tb and ka == kb
         bad += [] if same else [unit]
-        print("%-28s %10d %8d  %-12s %s" % (unit, len(ta or b""), len(ka), hashlib.sha256(ta or b"").hexdigest()[:12],
+        print("%-40s %10d %8d  %-12s %s" % (unit, len(ta or b""), len(ka), hashlib.sha256(ta or b"").hexdigest()[:12],
                                             "identical" if same else "DIFFERENT (text %s, descriptors %s)" % (ta == tb, ka == kb)))
+    for unit in sorted(set(b) - set(a)):
+        tb = text_bytes(b[unit])
+        print("%-40s %10d %8d  %-12s %s" % (unit, len(tb or b""), len(kernel_descriptors(b[unit])),
+                                            hashlib.sha256(tb or b"").hexdigest()[:12], "added"))
     print("%d units compared; %s" % (len(set(a) & set(b)), "all identical" if not bad else "DIFFERENT or unmatched: %s" % bad))
     sys.exit(1 if bad else 0)
