@@ -101,7 +101,8 @@ SOLVER_LIBRARIES = {lib.name: lib for lib in (
     Library("libhode_neural_odd.so", PKG + "/csrc/neural_odd", "include/hode_neural_odd.h",
             tuple(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_lanes.hpp", "hode_roche.hpp", "hode_host.hpp",
                                                "hode_dopri5_kernels.hpp", "hode_neural_args.hpp", "hode_neural_mf.hpp",
-                                               "hode_neural_mf_kernels.hpp", "hode_neural_dopri5_kernels.hpp"))
+                                               "hode_neural_mf_kernels.hpp", "hode_neural_dopri5_kernels.hpp",
+                                               "hode_adaptive_host.hpp", "hode_error_state.hpp"))
             + ("include/hode.h",), _neural_odd_units),
 )}
 

@@ -1,28 +1,11 @@
 // C-ABI entry points of libhode.so (declared in include/hode.h): argument checks, variant selection, launches.
-#include <stdarg.h>
-#include <stdio.h>
 #include <stdlib.h>
 
+#include "hode_error_state.hpp"  // hode::fail / hip_fail and the message behind hode_last_error_string: defined here, once
 #include "hode_host.hpp"
 #include "hode_roche.hpp"
 
 namespace hode {
-
-static thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-int hip_fail(hipError_t e, const char* what) {
-  if (e == hipSuccess) return 0;
-  snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-  return (int)e;
-}
 
 // out[j] += sum over waves of partials[w][j].  One wave per output element: lane l adds rows l, l+64, ... in order,
 // then a fixed-shape butterfly folds the 64 lane sums -- the summation tree depends only on (n_waves), so the

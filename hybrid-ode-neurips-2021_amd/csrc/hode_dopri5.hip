@@ -1,7 +1,9 @@
-// C-ABI entry points hode_dopri5_fwd / hode_dopri5_bwd (include/hode.h): workspace carving, the attempt loop, checks.
+// C-ABI entry points hode_dopri5_fwd / hode_dopri5_bwd (include/hode.h): checks, the Roche kernels' arguments and launches.
+// The workspace carving, the chunk policy and the attempt loop are hode_adaptive_host.hpp's, shared with the NeuralODE.
 #include <stdlib.h>
 #include <string.h>
 
+#include "hode_adaptive_host.hpp"
 #include "hode_dopri5_kernels.hpp"
 
 namespace {
@@ -10,27 +12,9 @@ using hode::DpArgs;
 using hode::DpCtrl;
 using hode::DpLaunch;
 
-// Attempts enqueued between two reads of the controller record.  Every read is a host round trip during which the GPU
-// idles (~70 us measured: 29-30 ms per solve with a fixed chunk of 32, 26.7 ms with 128 at 4 200 attempts), every attempt
-// enqueued past the end costs an early-exit launch (~1.3 us).  The chunk therefore starts small, doubles while nothing is
-// known, and then follows an estimate of what is left: attempts so far scaled by the output-grid progress j_next / T.
-constexpr int kChunkFirst = 64, kChunkMin = 32, kChunkMax = 2048;
+// attempts between two reads of the controller record (hode_adaptive_host.hpp): first / min / max
+constexpr hode::ChunkPolicy kChunks = {64, 32, 2048};
 constexpr int kAttemptWavesPerBlock = 1;
-
-int next_chunk(int chunk, long long attempts, int j_next, int n_times) {
-  const double done = n_times > 1 ? (double)(j_next - 1) / (double)(n_times - 1) : 1.0;
-  if (done <= 0.0) return chunk * 2 > kChunkMax ? kChunkMax : chunk * 2;
-  const double left = (double)attempts * (1.0 - done) / done;
-  long long c = (long long)(0.75 * left);
-  if (c < kChunkMin) c = kChunkMin;
-  if (c > kChunkMax) c = kChunkMax;
-  return (int)c;
-}
-
-size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-constexpr size_t kInitOffset = 128;  // DpInit sits behind the two DpCtrl records
-static_assert(2 * sizeof(DpCtrl) <= kInitOffset, "controller records overlap the init record");
-static_assert(sizeof(hode::DpInit) == sizeof(hode_dopri5_init_record), "DpInit is the ABI's hode_dopri5_init_record");
 
 // Patients per wave of the dopri5 kernels: full waves.  The fixed-grid kernels spread a small batch over ~one wave per
 // SIMD (hode::patients_per_wave) because they stream h every step; an attempt launch has no such stream, its cost per
@@ -43,30 +27,16 @@ int dp_n_waves(const hode_solve_desc* d) {
   return (d->batch + ppw - 1) / ppw;
 }
 
-struct DpLayout {
-  size_t ctrl, partials, slots, kbuf, tape_t, tape_dt, tape_j, tape_y, grad_partials, total;
-};
+using hode::AdaptiveLayout;
+using hode::kInitOffset;
 
-DpLayout dp_layout(const hode_solve_desc* d) {
+AdaptiveLayout dp_layout(const hode_solve_desc* d) {
   const int nw = dp_n_waves(d);
-  const size_t BD = (size_t)d->batch * d->latent_dim;
-  const size_t S = (size_t)(d->max_steps > 0 ? d->max_steps : 1);
-  DpLayout L;
-  size_t off = 0;
-  L.ctrl = off; off = align_up(off + kInitOffset + sizeof(hode::DpInit));  // two controller records + the DpInit record
-  L.partials = off; off = align_up(off + (size_t)4 * nw * sizeof(float));
-  L.slots = off; off = align_up(off + (size_t)2 * nw * sizeof(unsigned long long));
-  L.kbuf = off; off = align_up(off + 7 * BD * sizeof(float));
-  L.tape_t = off; off = align_up(off + S * sizeof(double));
-  L.tape_dt = off; off = align_up(off + S * sizeof(double));
-  L.tape_j = off; off = align_up(off + 2 * S * sizeof(int));
-  L.tape_y = off; off = align_up(off + ((d->flags & HODE_FLAG_NO_TAPE) ? 2 : S + 1) * BD * sizeof(float));
-  L.grad_partials = off; off = align_up(off + (size_t)nw * hode::n_partials(d) * sizeof(float));
-  L.total = off;
-  return L;
+  return hode::adaptive_layout(nw, (size_t)d->batch * d->latent_dim, d->max_steps, d->flags & HODE_FLAG_NO_TAPE,
+                               (size_t)2 * nw * sizeof(unsigned long long), hode::n_partials(d));
 }
 
-DpArgs dp_args(const hode_solve_desc* d, const DpLayout& L) {
+DpArgs dp_args(const hode_solve_desc* d, const AdaptiveLayout& L) {
   DpArgs a{};
   char* ws = (char*)d->workspace;
   a.t = d->t; a.y0 = d->y0; a.dosage = d->dosage; a.dose_times = d->dose_times; a.theta = d->theta;
@@ -133,7 +103,7 @@ int check_dp(const hode_solve_desc* d, bool bwd) {
     return hode::fail(HODE_E_UNSUPPORTED, "rhs_kind %d has no dopri5 kernels (have ROCHE, ROCHE_ABLATE, NEURAL)", d->rhs_kind);
   if (!d->theta) return hode::fail(HODE_E_NULL, "theta must be non-NULL");
   if (d->latent_dim > 4 && (!d->w1 || !d->b1)) return hode::fail(HODE_E_NULL, "w1 / b1 required when latent_dim > 4");
-  const DpLayout L = dp_layout(d);
+  const AdaptiveLayout L = dp_layout(d);
   if (!d->workspace || d->workspace_bytes < L.total)
     return hode::fail(HODE_E_WORKSPACE, "workspace %zu B < required %zu B", d->workspace_bytes, L.total);
   return 0;
@@ -152,7 +122,7 @@ extern "C" int hode_dopri5_fwd(const hode_solve_desc* d, void* stream) {
   }
   if (int e = check_dp(d, false)) return e;
   hipStream_t s = (hipStream_t)stream;
-  const DpLayout lay = dp_layout(d);
+  const AdaptiveLayout lay = dp_layout(d);
   DpArgs a = dp_args(d, lay);
   DpLaunch L;
   L.lpp = hode::choose_lpp(d);
@@ -179,9 +149,7 @@ extern "C" int hode_dopri5_fwd(const hode_solve_desc* d, void* stream) {
     a.hill2 = (hill[0] == 2.0f && hill[1] == 2.0f) ? 1 : 0;
   }
   DpCtrl host{};
-  int attempt = 0;
-  // every attempt either accepts (<= max_steps of those) or shrinks dt by >= 5x towards underflow: a generous bound
-  const long long max_attempts = 64LL * ((long long)d->max_steps + 64);
+  const long long max_attempts = hode::adaptive_max_attempts(d);
   // Experiment builds only (-DHODE_DP_EXPERIMENTS, then HODE_DP_PERSIST=1, quad layout): the whole attempt loop in one persistent launch (dp_persist_body_own: state in
   // registers, one hop through memory per attempt instead of a kernel boundary).  Correct and bounded, but MEASURED SLOWER on
   // this part -- 7.0 us per attempt against 5.7 (tools/dp_persist_probe.py): a fence-free, atomics-free all-to-all exchange
@@ -211,32 +179,14 @@ extern "C" int hode_dopri5_fwd(const hode_solve_desc* d, void* stream) {
     }
   }
   L.phase = 2;
-  int chunk = kChunkFirst;
-  while (!persist) {
-    for (int i = 0; i < chunk; ++i) {
-      a.attempt = attempt++;
-      if (int e = dp_dispatch_dim(d, L, a, s)) return e;
-    }
-    // the ONE host synchronisation of the path: the number of adaptive steps is data dependent
-    if (int e = hode::hip_fail(hipMemcpyAsync(&host, a.ctrl + (attempt & 1), sizeof(DpCtrl), hipMemcpyDeviceToHost, s),
-                               "controller read-back"))
-      return e;
-    if (int e = hode::hip_fail(hipStreamSynchronize(s), "controller read-back sync")) return e;
-    if (host.done) break;
-    if (attempt > max_attempts) {
-      host.status |= HODE_STATUS_MAX_STEPS;
-      break;
-    }
-    chunk = next_chunk(chunk, attempt, host.j_next, d->n_times);
+  if (!persist) {
+    const auto enqueue = [&](int i) {
+      a.attempt = i;
+      return dp_dispatch_dim(d, L, a, s);  // checks its own launch
+    };
+    if (int e = hode::adaptive_attempts(d, a.ctrl, kChunks, "dopri5 attempt launch", s, enqueue, &host)) return e;
   }
-  *d->host_n_accepted = host.n_acc;
-  if (d->host_n_rejected) *d->host_n_rejected = host.n_rej;
-  if (d->status && host.status) {
-    if (int e = hode::hip_fail(hipMemcpyAsync(d->status, &host.status, sizeof(int), hipMemcpyHostToDevice, s), "status write"))
-      return e;
-    if (int e = hode::hip_fail(hipStreamSynchronize(s), "status write sync")) return e;
-  }
-  return 0;
+  return hode::adaptive_report(d, host, s);
 }
 
 extern "C" int hode_dopri5_bwd(const hode_solve_desc* d, void* stream) {
@@ -246,7 +196,7 @@ extern "C" int hode_dopri5_bwd(const hode_solve_desc* d, void* stream) {
   }
   if (int e = check_dp(d, true)) return e;
   hipStream_t s = (hipStream_t)stream;
-  const DpLayout lay = dp_layout(d);
+  const AdaptiveLayout lay = dp_layout(d);
   DpArgs a = dp_args(d, lay);
   a.n_acc = *d->host_n_accepted;
   if (a.n_acc < 0 || a.n_acc > d->max_steps) return hode::fail(HODE_E_SIZE, "n_accepted %d outside the tape", a.n_acc);
@@ -275,11 +225,6 @@ extern "C" int hode_dopri5_tape_offsets(const hode_solve_desc* d, size_t* out5) 
   if (!d || !out5) return hode::fail(HODE_E_NULL, "descriptor / out5 is NULL");
   if (d->struct_size != sizeof(hode_solve_desc)) return hode::fail(HODE_E_SIZE, "struct_size mismatch");
   if (is_neural(d)) return hode::neural_dopri5_tape_offsets(d, out5);
-  const DpLayout L = dp_layout(d);
-  out5[0] = L.ctrl + kInitOffset;
-  out5[1] = L.tape_t;
-  out5[2] = L.tape_dt;
-  out5[3] = L.tape_j;
-  out5[4] = L.tape_y;
+  hode::adaptive_tape_offsets(dp_layout(d), out5);
   return 0;
 }

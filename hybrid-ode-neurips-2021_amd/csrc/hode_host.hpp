@@ -1,4 +1,4 @@
-// Host-side declarations shared by the translation units of libhode.so.
+// Host-side declarations shared by the translation units of libhode.so (fail / hip_fail: of libhode_neural_odd.so too).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -6,7 +6,8 @@
 
 namespace hode {
 
-// records a thread-local message (returned by hode_last_error_string) and returns `code`
+// records a thread-local message (returned by the library's *_last_error_string) and returns `code`; defined, with hip_fail
+// below, by hode_error_state.hpp in one unit per library
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // kernel arguments of the fixed-grid Roche kernels (device pointers + sizes), see hode_rk_kernels.hpp
@@ -47,6 +48,11 @@ int dp_dispatch_d6(const DpLaunch&, const DpArgs&, hipStream_t);
 int dp_dispatch_d8(const DpLaunch&, const DpArgs&, hipStream_t);
 int dp_dispatch_d12(const DpLaunch&, const DpArgs&, hipStream_t);
 
+// Latent dimensions at which libhode.so holds the matrix-core NeuralODE kernels, fixed grid (hode_neural_mf.hip) and adaptive
+// (hode_neural_dopri5.hip): the state [y, Dose, 1] must fit ONE 16-row tile (D + 2 <= 16); the reference's simulation
+// configs use 6 (its default, sim_config.py:25), 8 and 12.  The odd sizes 5 .. 15 are libhode_neural_odd.so's.
+#define HODE_NEURAL_DIMS(X) X(4) X(6) X(8) X(10) X(12) X(14)
+
 // neural rhs (hode_neural.hip)
 size_t neural_workspace_bytes(const hode_solve_desc* d, bool bwd);
 int neural_rk(const hode_solve_desc* d, bool bwd, hipStream_t s);
@@ -82,8 +88,9 @@ int split_rk_fwd(const hode_solve_desc* d, hipStream_t s);
 size_t split_workspace_bytes(const hode_solve_desc* d);
 int split_rk_bwd(const hode_solve_desc* d, hipStream_t s);
 
-// shared host helpers (hode_api.hip)
+// 0 for hipSuccess; otherwise records "<what>: <HIP's text>" and returns the HIP error as the code (hode_error_state.hpp)
 int hip_fail(hipError_t e, const char* what);
+// shared host helpers (hode_api.hip)
 int patients_per_wave(int B, int lpp);
 int n_waves_for(int B, int lpp);
 int choose_lpp(const hode_solve_desc* d);

@@ -21,62 +21,31 @@
 // layer-1 input) and dW2 in 2 x HT accumulator tiles for the whole sweep.  One partial block per wave, folded in a fixed
 // order by neural_grad_fold_kernel (deterministic; no operand tape in HBM, no host GEMM).
 //
-// The kernel templates, the workspace layout and the forward's host loop are in hode_neural_dopri5_kernels.hpp; this file
-// keeps the backward's launch sequence and the dispatch over the latent dimensions libhode.so holds (the even ones; the
-// odd ones 5 .. 15 are instantiated from the same header by neural_odd/hode_neural_odd_dim.hip for libhode_neural_odd.so).
+// The kernel templates and the host templates that launch them (nd_fwd, nd_bwd) are in hode_neural_dopri5_kernels.hpp; this
+// file keeps the dispatch over the latent dimensions libhode.so holds (HODE_NEURAL_DIMS, hode_host.hpp; the odd ones
+// 5 .. 15 are instantiated from the same header by neural_odd/hode_neural_odd_dim.hip for libhode_neural_odd.so).
 #include <hip/hip_runtime.h>
 
 #include "hode_neural_dopri5_kernels.hpp"
 
 namespace hode {
 
-namespace {
-
-template <int D>
-int nd_bwd(const hode_solve_desc* d, hipStream_t s) {
-  const NdLayout lay = nd_layout<D>(d);
-  if (!d->workspace || d->workspace_bytes < lay.total)
-    return fail(HODE_E_WORKSPACE, "workspace %zu B < required %zu B", d->workspace_bytes, lay.total);
-  NdpArgs a = nd_args<D>(d, lay);
-  a.n_acc = *d->host_n_accepted;
-  if (a.n_acc < 0 || a.n_acc > d->max_steps) return fail(HODE_E_SIZE, "n_accepted %d outside the tape", a.n_acc);
-  const dim3 grid(a.n_waves), block(64);
-  const dim3 fgrid(NeuralGradAcc<D>::NP);
-  hipLaunchKernelGGL((ndp_bwd_kernel<D>), grid, block, 0, s, a);
-  hipLaunchKernelGGL((neural_grad_fold_kernel<D>), fgrid, block, 0, s, a.grad_partials, a.n_waves, a.grad_w1, a.grad_b1, a.grad_w2, a.grad_b2);
-  if (a.n_acc > 0 && !(d->flags & HODE_FLAG_DETACH_FIRST_STEP)) {
-    hipLaunchKernelGGL((ndp_initbwd_kernel<D, 1>), grid, block, 0, s, a);
-    hipLaunchKernelGGL((ndp_initbwd_kernel<D, 2>), grid, block, 0, s, a);
-    hipLaunchKernelGGL((neural_grad_fold_kernel<D>), fgrid, block, 0, s, a.grad_partials, a.n_waves, a.grad_w1, a.grad_b1, a.grad_w2, a.grad_b2);
-  }
-  return hip_fail(hipGetLastError(), "neural dopri5 backward launch");
-}
-
-}  // namespace
-
-// Latent dimensions with a compiled kernel: the state [y, Dose, 1] must fit ONE 16-row tile (D + 2 <= 16); the reference's
-// simulation configs use 6 (its default, sim_config.py:25), 8 and 12.
-#define HODE_ND_DIMS(X) X(4) X(6) X(8) X(10) X(12) X(14)
-
 size_t neural_dopri5_workspace_bytes(const hode_solve_desc* d) {
   switch (d->latent_dim) {
 #define HODE_ND_CASE(n) case n: return nd_layout<n>(d).total;
-    HODE_ND_DIMS(HODE_ND_CASE)
+    HODE_NEURAL_DIMS(HODE_ND_CASE)
 #undef HODE_ND_CASE
   }
   return 0;
 }
 
 int neural_dopri5_tape_offsets(const hode_solve_desc* d, size_t* out5) {
-  NdLayout L;
   switch (d->latent_dim) {
-#define HODE_ND_CASE(n) case n: L = nd_layout<n>(d); break;
-    HODE_ND_DIMS(HODE_ND_CASE)
+#define HODE_ND_CASE(n) case n: adaptive_tape_offsets(nd_layout<n>(d), out5); return 0;
+    HODE_NEURAL_DIMS(HODE_ND_CASE)
 #undef HODE_ND_CASE
-    default: return fail(HODE_E_UNSUPPORTED, "neural dopri5: latent_dim %d has no compiled kernel (have 4, 6, 8, 10, 12, 14)", d->latent_dim);
   }
-  out5[0] = L.ctrl + kNdInitOffset; out5[1] = L.tape_t; out5[2] = L.tape_dt; out5[3] = L.tape_j; out5[4] = L.tape_y;
-  return 0;
+  return fail(HODE_E_UNSUPPORTED, "neural dopri5: latent_dim %d has no compiled kernel (have 4, 6, 8, 10, 12, 14)", d->latent_dim);
 }
 
 int neural_dopri5(const hode_solve_desc* d, bool bwd, hipStream_t s) {
@@ -85,7 +54,7 @@ int neural_dopri5(const hode_solve_desc* d, bool bwd, hipStream_t s) {
   if (!d->w1 || !d->b1 || !d->w2 || !d->b2) return fail(HODE_E_NULL, "neural dopri5: w1 / b1 / w2 / b2 required");
   switch (d->latent_dim) {
 #define HODE_ND_CASE(n) case n: return bwd ? nd_bwd<n>(d, s) : nd_fwd<n>(d, s);
-    HODE_ND_DIMS(HODE_ND_CASE)
+    HODE_NEURAL_DIMS(HODE_ND_CASE)
 #undef HODE_ND_CASE
   }
   return fail(HODE_E_UNSUPPORTED, "neural dopri5: latent_dim %d has no compiled kernel (have 4, 6, 8, 10, 12, 14)", d->latent_dim);

@@ -1,10 +1,12 @@
 // Kernel templates of the adaptive NeuralODE solve (hode_neural_dopri5.hip has the description): the attempt kernels, the
-// backward sweep, the backward of the initial step size, and the host templates that lay the workspace out and run the
-// forward.  Instantiated by hode_neural_dopri5.hip for libhode.so (even latent dimensions) and by
-// neural_odd/hode_neural_odd_dim.hip for libhode_neural_odd.so (odd ones); nothing here is instantiated by inclusion.
+// backward sweep, the backward of the initial step size, and the host templates that launch them, nd_fwd and nd_bwd, on the
+// workspace carving, chunk policy and attempt loop of hode_adaptive_host.hpp.  Instantiated by hode_neural_dopri5.hip for
+// libhode.so (even latent dimensions) and by neural_odd/hode_neural_odd_dim.hip for libhode_neural_odd.so (odd ones);
+// nothing here is instantiated by inclusion.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "hode_adaptive_host.hpp"
 #include "hode_dopri5_kernels.hpp"
 #include "hode_neural_mf.hpp"
 
@@ -464,34 +466,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   }
 }
 // ------------------------------------------------------------------------------------------------ host side
-inline size_t nd_align(size_t x) { return (x + 255) / 256 * 256; }
-constexpr size_t kNdInitOffset = 128;
-
-struct NdLayout {
-  size_t ctrl, partials, kbuf, tape_t, tape_dt, tape_j, tape_y, grad_partials, total;
-};
-
+// the workspace of hode_adaptive_host.hpp without the Roche kernels' slots; one NeuralGradAcc block per wave
 template <int D>
-NdLayout nd_layout(const hode_solve_desc* d) {
-  const int nw = (d->batch + 15) / 16;
-  const size_t BD = (size_t)d->batch * D;
-  const size_t S = (size_t)(d->max_steps > 0 ? d->max_steps : 1);
-  NdLayout L;
-  size_t off = 0;
-  L.ctrl = off; off = nd_align(off + kNdInitOffset + sizeof(DpInit));
-  L.partials = off; off = nd_align(off + (size_t)4 * nw * sizeof(float));
-  L.kbuf = off; off = nd_align(off + 7 * BD * sizeof(float));
-  L.tape_t = off; off = nd_align(off + S * sizeof(double));
-  L.tape_dt = off; off = nd_align(off + S * sizeof(double));
-  L.tape_j = off; off = nd_align(off + 2 * S * sizeof(int));
-  L.tape_y = off; off = nd_align(off + ((d->flags & HODE_FLAG_NO_TAPE) ? 2 : S + 1) * BD * sizeof(float));
-  L.grad_partials = off; off = nd_align(off + (size_t)nw * NeuralGradAcc<D>::NP * sizeof(float));
-  L.total = off;
-  return L;
+AdaptiveLayout nd_layout(const hode_solve_desc* d) {
+  return adaptive_layout((d->batch + 15) / 16, (size_t)d->batch * D, d->max_steps, d->flags & HODE_FLAG_NO_TAPE, 0,
+                         NeuralGradAcc<D>::NP);
 }
 
 template <int D>
-NdpArgs nd_args(const hode_solve_desc* d, const NdLayout& L) {
+NdpArgs nd_args(const hode_solve_desc* d, const AdaptiveLayout& L) {
   NdpArgs a{};
   char* ws = (char*)d->workspace;
   a.nn.t = d->t; a.nn.y0 = d->y0; a.nn.dosage = d->dosage; a.nn.dose_times = d->dose_times;
@@ -499,7 +482,7 @@ NdpArgs nd_args(const hode_solve_desc* d, const NdLayout& L) {
   a.nn.h = d->h; a.nn.grad_h = d->grad_h; a.nn.grad_y0 = d->grad_y0;
   a.nn.B = d->batch; a.nn.T = d->n_times; a.nn.K = d->n_dose; a.nn.perturb = 0;
   a.ctrl = (DpCtrl*)(ws + L.ctrl);
-  a.init = (DpInit*)(ws + L.ctrl + kNdInitOffset);
+  a.init = (DpInit*)(ws + L.ctrl + kInitOffset);
   a.partials = (float*)(ws + L.partials);
   a.kbuf = (float*)(ws + L.kbuf);
   a.tape_t = (double*)(ws + L.tape_t);
@@ -515,18 +498,12 @@ NdpArgs nd_args(const hode_solve_desc* d, const NdLayout& L) {
   return a;
 }
 
-inline int nd_next_chunk(int chunk, long long attempts, int j_next, int n_times) {
-  const double done = n_times > 1 ? (double)(j_next - 1) / (double)(n_times - 1) : 1.0;
-  if (done <= 0.0) return chunk * 2 > 1024 ? 1024 : chunk * 2;
-  long long c = (long long)(0.75 * (double)attempts * (1.0 - done) / done);
-  if (c < 16) c = 16;
-  if (c > 1024) c = 1024;
-  return (int)c;
-}
+// attempts between two reads of the controller record (hode_adaptive_host.hpp): first / min / max
+constexpr ChunkPolicy kNdChunks = {32, 16, 1024};
 
 template <int D>
 int nd_fwd(const hode_solve_desc* d, hipStream_t s) {
-  const NdLayout lay = nd_layout<D>(d);
+  const AdaptiveLayout lay = nd_layout<D>(d);
   if (!d->workspace || d->workspace_bytes < lay.total)
     return fail(HODE_E_WORKSPACE, "workspace %zu B < required %zu B", d->workspace_bytes, lay.total);
   NdpArgs a = nd_args<D>(d, lay);
@@ -535,32 +512,36 @@ int nd_fwd(const hode_solve_desc* d, hipStream_t s) {
   hipLaunchKernelGGL((ndp_fwd_kernel<D, 1>), grid, block, 0, s, a);
   if (int e = hip_fail(hipGetLastError(), "neural dopri5 init launch")) return e;
   DpCtrl host{};
-  int attempt = 0, chunk = 32;
-  const long long max_attempts = 64LL * ((long long)d->max_steps + 64);
-  for (;;) {
-    for (int i = 0; i < chunk; ++i) {
-      a.attempt = attempt++;
-      hipLaunchKernelGGL((ndp_fwd_kernel<D, 2>), grid, block, 0, s, a);
-    }
-    if (int e = hip_fail(hipGetLastError(), "neural dopri5 attempt launch")) return e;
-    // the ONE host synchronisation of the path: the number of adaptive steps is data dependent
-    if (int e = hip_fail(hipMemcpyAsync(&host, a.ctrl + (attempt & 1), sizeof(DpCtrl), hipMemcpyDeviceToHost, s), "controller read-back"))
-      return e;
-    if (int e = hip_fail(hipStreamSynchronize(s), "controller read-back sync")) return e;
-    if (host.done) break;
-    if (attempt > max_attempts) {
-      host.status |= HODE_STATUS_MAX_STEPS;
-      break;
-    }
-    chunk = nd_next_chunk(chunk, attempt, host.j_next, d->n_times);
+  const auto enqueue = [&](int i) {
+    a.attempt = i;
+    hipLaunchKernelGGL((ndp_fwd_kernel<D, 2>), grid, block, 0, s, a);
+    return 0;  // the loop looks at hipGetLastError once per chunk
+  };
+  if (int e = adaptive_attempts(d, a.ctrl, kNdChunks, "neural dopri5 attempt launch", s, enqueue, &host)) return e;
+  return adaptive_report(d, host, s);
+}
+
+// the backward's launch sequence: the sweep over the tape and its fold, then (unless the first step is detached) the two
+// passes of the initial step size's backward and their fold.  (Internal linkage, like the helpers of hode_adaptive_host.hpp;
+// nd_fwd keeps the external linkage under which its instantiations are among the names both libraries have always held.)
+template <int D>
+static int nd_bwd(const hode_solve_desc* d, hipStream_t s) {
+  const AdaptiveLayout lay = nd_layout<D>(d);
+  if (!d->workspace || d->workspace_bytes < lay.total)
+    return fail(HODE_E_WORKSPACE, "workspace %zu B < required %zu B", d->workspace_bytes, lay.total);
+  NdpArgs a = nd_args<D>(d, lay);
+  a.n_acc = *d->host_n_accepted;
+  if (a.n_acc < 0 || a.n_acc > d->max_steps) return fail(HODE_E_SIZE, "n_accepted %d outside the tape", a.n_acc);
+  const dim3 grid(a.n_waves), block(64);
+  const dim3 fgrid(NeuralGradAcc<D>::NP);
+  hipLaunchKernelGGL((ndp_bwd_kernel<D>), grid, block, 0, s, a);
+  hipLaunchKernelGGL((neural_grad_fold_kernel<D>), fgrid, block, 0, s, a.grad_partials, a.n_waves, a.grad_w1, a.grad_b1, a.grad_w2, a.grad_b2);
+  if (a.n_acc > 0 && !(d->flags & HODE_FLAG_DETACH_FIRST_STEP)) {
+    hipLaunchKernelGGL((ndp_initbwd_kernel<D, 1>), grid, block, 0, s, a);
+    hipLaunchKernelGGL((ndp_initbwd_kernel<D, 2>), grid, block, 0, s, a);
+    hipLaunchKernelGGL((neural_grad_fold_kernel<D>), fgrid, block, 0, s, a.grad_partials, a.n_waves, a.grad_w1, a.grad_b1, a.grad_w2, a.grad_b2);
   }
-  *d->host_n_accepted = host.n_acc;
-  if (d->host_n_rejected) *d->host_n_rejected = host.n_rej;
-  if (d->status && host.status) {
-    if (int e = hip_fail(hipMemcpyAsync(d->status, &host.status, sizeof(int), hipMemcpyHostToDevice, s), "status write")) return e;
-    if (int e = hip_fail(hipStreamSynchronize(s), "status write sync")) return e;
-  }
-  return 0;
+  return hip_fail(hipGetLastError(), "neural dopri5 backward launch");
 }
 
 }  // namespace hode

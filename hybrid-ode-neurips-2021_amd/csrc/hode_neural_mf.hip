@@ -18,55 +18,35 @@
 // The weight gradients are outer products summed over patients: as in hode_neural.hip the backward tapes their operands
 // patient-minor for the caller's BLAS GEMMs (hode/neural.py) -- same offsets, same layout.
 //
-// The two kernel templates are in hode_neural_mf_kernels.hpp; this file keeps the launcher and the dispatch over the latent
-// dimensions libhode.so holds (the odd ones 5 .. 15: neural_odd/hode_neural_odd_dim.hip, libhode_neural_odd.so).
+// The two kernel templates and their launcher are in hode_neural_mf_kernels.hpp; this file keeps the dispatch over the latent
+// dimensions libhode.so holds (HODE_NEURAL_DIMS; the odd ones 5 .. 15: neural_odd/hode_neural_odd_dim.hip,
+// libhode_neural_odd.so).
 #include <hip/hip_runtime.h>
 
 #include "hode_neural_mf_kernels.hpp"
 
 namespace hode {
 
-template <int D>
-int launch_neural_mf_d(const hode_solve_desc* d, const NeuralArgs& a, bool bwd, hipStream_t s) {
-  const dim3 grid((d->batch + 15) / 16), block(64);
-  const bool onchip = bwd && d->grad_w1 != nullptr;
-#define HODE_NEURAL_MF_LAUNCH(M)                                                                   \
-  if (bwd && onchip) hipLaunchKernelGGL((neural_mf_bwd_kernel<D, M, true>), grid, block, 0, s, a);  \
-  else if (bwd) hipLaunchKernelGGL((neural_mf_bwd_kernel<D, M, false>), grid, block, 0, s, a);      \
-  else hipLaunchKernelGGL((neural_mf_fwd_kernel<D, M>), grid, block, 0, s, a);
-  switch (d->method) {
-    case HODE_METHOD_EULER: HODE_NEURAL_MF_LAUNCH(HODE_METHOD_EULER) break;
-    case HODE_METHOD_MIDPOINT: HODE_NEURAL_MF_LAUNCH(HODE_METHOD_MIDPOINT) break;
-    default: HODE_NEURAL_MF_LAUNCH(HODE_METHOD_RK4_38) break;
-  }
-  if (onchip)
-    hipLaunchKernelGGL((neural_grad_fold_kernel<D>), dim3(NeuralGradAcc<D>::NP), block, 0, s, a.a1t, (int)grid.x, d->grad_w1,
-                       d->grad_b1, d->grad_w2, d->grad_b2);
-  return hip_fail(hipGetLastError(), "neural MFMA kernel launch");
-}
+// hode_workspace_bytes asks for the partials of any latent_dim, also one nobody serves (the launch is refused by
+// check_neural): such a size has always been answered, and launched, as this one
+constexpr int kUnlistedDim = 12;
 
-// bytes of per-wave gradient partials the on-chip backward needs (it uses the a1t slot of the workspace for them)
 size_t neural_mf_partial_bytes(const hode_solve_desc* d) {
-  const size_t nw = (d->batch + 15) / 16;
   switch (d->latent_dim) {
-    case 4: return nw * NeuralGradAcc<4>::NP * sizeof(float);
-    case 6: return nw * NeuralGradAcc<6>::NP * sizeof(float);
-    case 8: return nw * NeuralGradAcc<8>::NP * sizeof(float);
-    case 10: return nw * NeuralGradAcc<10>::NP * sizeof(float);
-    case 14: return nw * NeuralGradAcc<14>::NP * sizeof(float);
-    default: return nw * NeuralGradAcc<12>::NP * sizeof(float);
+#define HODE_NEURAL_MF_CASE(n) case n: return neural_mf_partial_bytes_d<n>(d);
+    HODE_NEURAL_DIMS(HODE_NEURAL_MF_CASE)
+#undef HODE_NEURAL_MF_CASE
   }
+  return neural_mf_partial_bytes_d<kUnlistedDim>(d);
 }
 
 int launch_neural_mf(const hode_solve_desc* d, const NeuralArgs& a, bool bwd, hipStream_t s) {
   switch (d->latent_dim) {   // check_neural admits 4, 6, ..., 14: [y, Dose, 1] fits one 16-row tile
-    case 4: return launch_neural_mf_d<4>(d, a, bwd, s);
-    case 6: return launch_neural_mf_d<6>(d, a, bwd, s);
-    case 8: return launch_neural_mf_d<8>(d, a, bwd, s);
-    case 10: return launch_neural_mf_d<10>(d, a, bwd, s);
-    case 14: return launch_neural_mf_d<14>(d, a, bwd, s);
-    default: return launch_neural_mf_d<12>(d, a, bwd, s);
+#define HODE_NEURAL_MF_CASE(n) case n: return launch_neural_mf_d<n, true>(d, a, bwd, s);
+    HODE_NEURAL_DIMS(HODE_NEURAL_MF_CASE)
+#undef HODE_NEURAL_MF_CASE
   }
+  return launch_neural_mf_d<kUnlistedDim, true>(d, a, bwd, s);
 }
 
 }  // namespace hode

@@ -1,6 +1,6 @@
 // Kernel templates of the fixed-grid NeuralODE solve on the matrix cores (hode_neural_mf.hip has the description of the
-// layout).  Instantiated by hode_neural_mf.hip for libhode.so (even latent dimensions) and by
-// neural_odd/hode_neural_odd_dim.hip for libhode_neural_odd.so (odd ones).
+// layout), and the host templates that launch them.  Instantiated by hode_neural_mf.hip for libhode.so (even latent
+// dimensions) and by neural_odd/hode_neural_odd_dim.hip for libhode_neural_odd.so (odd ones).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -167,6 +167,39 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   }
   mf_store_rows<D>(a.grad_y0 + (size_t)p * D, g, lam, live);
   if constexpr (ONCHIP) acc.store(a.a1t + (size_t)blockIdx.x * NeuralGradAcc<D>::NP, lane);
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+// (internal linkage: helpers of the unit that instantiates them, not names of its library)
+// bytes of per-wave gradient partials the on-chip backward needs (it uses the a1t slot of the workspace for them)
+template <int D>
+static size_t neural_mf_partial_bytes_d(const hode_solve_desc* d) {
+  return (size_t)((d->batch + 15) / 16) * NeuralGradAcc<D>::NP * sizeof(float);
+}
+
+// One fixed-grid solve or its backward.  With grad_w1 the backward accumulates the weight gradients on chip and folds the
+// per-wave partials; without it, it tapes their operands for the caller -- an instantiation that exists only where
+// OPERAND_TAPE is set (libhode.so; libhode_neural_odd.so holds the on-chip backward alone and refuses such a call).
+template <int D, bool OPERAND_TAPE>
+static int launch_neural_mf_d(const hode_solve_desc* d, const NeuralArgs& a, bool bwd, hipStream_t s) {
+  const dim3 grid((d->batch + 15) / 16), block(64);
+  const bool onchip = bwd && d->grad_w1 != nullptr;
+  if (!OPERAND_TAPE && bwd && !onchip) return fail(HODE_E_UNSUPPORTED, "neural MFMA backward: the operand-tape mode is not built here");
+#define HODE_NEURAL_MF_LAUNCH(M)                                                                      \
+  if (bwd && onchip) hipLaunchKernelGGL((neural_mf_bwd_kernel<D, M, true>), grid, block, 0, s, a);     \
+  else if (bwd) {                                                                                     \
+    if constexpr (OPERAND_TAPE) hipLaunchKernelGGL((neural_mf_bwd_kernel<D, M, false>), grid, block, 0, s, a); \
+  } else hipLaunchKernelGGL((neural_mf_fwd_kernel<D, M>), grid, block, 0, s, a);
+  switch (d->method) {
+    case HODE_METHOD_EULER: HODE_NEURAL_MF_LAUNCH(HODE_METHOD_EULER) break;
+    case HODE_METHOD_MIDPOINT: HODE_NEURAL_MF_LAUNCH(HODE_METHOD_MIDPOINT) break;
+    default: HODE_NEURAL_MF_LAUNCH(HODE_METHOD_RK4_38) break;
+  }
+#undef HODE_NEURAL_MF_LAUNCH
+  if (onchip)
+    hipLaunchKernelGGL((neural_grad_fold_kernel<D>), dim3(NeuralGradAcc<D>::NP), block, 0, s, a.a1t, (int)grid.x, d->grad_w1,
+                       d->grad_b1, d->grad_w2, d->grad_b2);
+  return hip_fail(hipGetLastError(), "neural MFMA kernel launch");
 }
 
 }  // namespace hode

@@ -4,34 +4,12 @@
 // kernel symbols is pinned, not because the code differs.  At D = 15 [y, Dose] fills the 16-row input tile exactly and the
 // layer-1 bias gradient takes NeuralGradAcc's path without the ones row (../hode_neural_mf.hpp).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
+#include "../hode_error_state.hpp"  // hode::fail / hip_fail for this library's units: defined here, once
 #include "../hode_host.hpp"
 #include "../hode_neural_args.hpp"
 #include "hode_neural_odd.hpp"
-
-namespace hode {
-
-static thread_local char g_odd_err[512] = "";
-
-// the two error helpers the shared host templates call (declared in ../hode_host.hpp); this library's own copies
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_odd_err, sizeof(g_odd_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-int hip_fail(hipError_t e, const char* what) {
-  if (e == hipSuccess) return 0;
-  snprintf(g_odd_err, sizeof(g_odd_err), "%s: %s", what, hipGetErrorString(e));
-  return (int)e;
-}
-
-}  // namespace hode
 
 namespace {
 
@@ -117,7 +95,7 @@ hode::NeuralArgs rk_args(const hode_solve_desc* d) {
 
 extern "C" int hode_neural_odd_version(void) { return HODE_NEURAL_ODD_ABI_VERSION; }
 
-extern "C" const char* hode_neural_odd_last_error_string(void) { return hode::g_odd_err; }
+extern "C" const char* hode_neural_odd_last_error_string(void) { return hode::g_err; }
 
 extern "C" size_t hode_neural_odd_workspace_bytes(const hode_solve_desc* d, int which) {
   const NeuralOddDim* e = nullptr;

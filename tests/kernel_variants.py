@@ -191,9 +191,9 @@ def neural_layout(D, lanes=0):
 
 def neural_fixed(D, method, lanes=0, onchip=True):
     """Fixed-grid NeuralODE forward + backward (onchip = the caller hands grad_w1, hode.neural's default).
-    mf: csrc/hode_neural_mf.hip:188-203 launch_neural_mf_d: grid ceil(B/16); neural_mf_bwd_kernel<D, M, ONCHIP> with
-    ONCHIP = bwd && grad_w1 (:190), and the on-chip backward folds its per-wave partials with neural_grad_fold_kernel<D>
-    (:200).  lane: csrc/hode_neural.hip:320-330 launch_neural: grid ceil(B/64), after transpose_w2_kernel (:360, every
+    mf: csrc/hode_neural_mf_kernels.hpp launch_neural_mf_d: grid ceil(B/16); neural_mf_bwd_kernel<D, M, ONCHIP> with
+    ONCHIP = bwd && grad_w1, and the on-chip backward folds its per-wave partials with neural_grad_fold_kernel<D>.
+    lane: csrc/hode_neural.hip:320-330 launch_neural: grid ceil(B/64), after transpose_w2_kernel (:360, every
     call); its backward always writes the operand tapes (csrc/hode_neural.hip:276 neural_onchip)."""
     if neural_layout(D, lanes) == "lane":
         return ["hode::transpose_w2_kernel", "hode::neural_fwd_kernel<%d, %d>" % (D, method),
@@ -209,16 +209,16 @@ def neural_lanes(case):
 
 
 def neural_grid(B, layout):
-    """Workgroups of one launch: csrc/hode_neural_mf.hip:189 (16 patients per wave), csrc/hode_neural.hip:321 (64)."""
+    """Workgroups of one launch: csrc/hode_neural_mf_kernels.hpp launch_neural_mf_d (16 patients per wave), csrc/hode_neural.hip:321 (64)."""
     return (B + 15) // 16 if layout == "mf" else (B + 63) // 64
 
 
-NEURAL_DOPRI5_DIMS = (4, 6, 8, 10, 12, 14)  # csrc/hode_neural_dopri5.hip:610 HODE_ND_DIMS
+NEURAL_DOPRI5_DIMS = (4, 6, 8, 10, 12, 14)  # csrc/hode_host.hpp HODE_NEURAL_DIMS
 
 
 def neural_dopri5_kernels(D, n_acc, detach_first_step):
-    """csrc/hode_neural_dopri5.hip:554-563 nd_fwd: phases 0 / 1 (initial step) and 2 (attempts) of ndp_fwd_kernel<D, PHASE>;
-    :596-602 nd_bwd: ndp_bwd_kernel<D> and the fold of its partials, then, when a step was accepted (n_acc > 0) and the
+    """csrc/hode_neural_dopri5_kernels.hpp nd_fwd: phases 0 / 1 (initial step) and 2 (attempts) of ndp_fwd_kernel<D, PHASE>;
+    nd_bwd (same header): ndp_bwd_kernel<D> and the fold of its partials, then, when a step was accepted (n_acc > 0) and the
     first step size is not detached (HODE_FLAG_DETACH_FIRST_STEP), ndp_initbwd_kernel<D, 1>, <D, 2> and the fold again."""
     out = ["hode::ndp_fwd_kernel<%d, %d>" % (D, ph) for ph in (0, 1, 2)]
     out += ["hode::ndp_bwd_kernel<%d>" % D, "hode::neural_grad_fold_kernel<%d>" % D]
@@ -612,7 +612,7 @@ def _readout_cases():
     return out
 
 
-NEURAL_DIMS = (4, 6, 8, 10, 12, 14)  # csrc/hode_neural_mf.hip:220-227 launch_neural_mf (check_neural: even, 4..14)
+NEURAL_DIMS = (4, 6, 8, 10, 12, 14)  # csrc/hode_host.hpp HODE_NEURAL_DIMS (check_neural: even, 4..14)
 NEURAL_LANE_DIMS = (6, 8, 12)        # csrc/hode_neural.hip:358-366
 READOUT_LATENT = (4, 6, 8, 12)       # csrc/hode_readout.hip:342-347
 NEW_FAMILIES = ("neural", "neural_dopri5", "lstm", "readout", "readout_mlp")  # CASES families of the kernels below

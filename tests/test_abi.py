@@ -87,6 +87,13 @@ def test_workspace_query(lib):
     assert n20 % ((16 * 20 + 16 + 15) * 4) == 0
 
 
+def test_adaptive_workspace_layouts_are_the_recorded_ones(lib):
+    """Totals and tape offsets of the dopri5 workspace, Roche at D 4 / 12 and NeuralODE at D 4 / 14, to the byte."""
+    import adaptive_layout_table
+    adaptive_layout_table.assert_layouts(lib.hode_workspace_bytes, lib.hode_dopri5_tape_offsets,
+                                         {("ROCHE", 4), ("ROCHE", 12), ("NEURAL", 4), ("NEURAL", 14)})
+
+
 def _variant_sizes(lib, forced):
     """Workspace sizes of five calls whose kernel variant has a switch; `forced` selects the non-default variant through
     the descriptor field (quad Roche layout, lane-per-patient neural / real kernels, NT = 1, the lane readout kernel)."""

@@ -424,11 +424,15 @@ def test_neural_source_pins_the_restated_rules():
     assert "bool neural_onchip(const hode_solve_desc* d) { return !neural_lanes(d) && d->grad_w1 != nullptr; }" in nh
     assert "if (D != 6 && D != 8 && D != 12)" in nh
     assert "const dim3 grid((d->batch + 63) / 64), block(64);" in nh
-    mf = _norm(_strip_and_expand(open(os.path.join(CSRC, "hode_neural_mf.hip")).read()))
+    # the launchers are next to the kernel templates they launch; the list of sizes serves both dispatch files
+    mf = _norm(_strip_and_expand(open(os.path.join(CSRC, "hode_neural_mf_kernels.hpp")).read()))
     assert "const dim3 grid((d->batch + 15) / 16), block(64); const bool onchip = bwd && d->grad_w1 != nullptr;" in mf
-    raw = open(os.path.join(CSRC, "hode_neural_dopri5.hip")).read()
-    assert "#define HODE_ND_DIMS(X) " + " ".join("X(%d)" % D for D in kv.NEURAL_DOPRI5_DIMS) + "\n" in raw
-    nd = _norm(_strip_and_expand(raw))
+    assert kv.NEURAL_DOPRI5_DIMS == kv.NEURAL_DIMS
+    raw = open(os.path.join(CSRC, "hode_host.hpp")).read()
+    assert "#define HODE_NEURAL_DIMS(X) " + " ".join("X(%d)" % D for D in kv.NEURAL_DOPRI5_DIMS) + "\n" in raw
+    for unit in ("hode_neural_mf.hip", "hode_neural_dopri5.hip"):
+        assert "HODE_NEURAL_DIMS(" in open(os.path.join(CSRC, unit)).read()
+    nd = _norm(_strip_and_expand(open(os.path.join(CSRC, "hode_neural_dopri5_kernels.hpp")).read()))
     assert "if (a.n_acc > 0 && !(d->flags & HODE_FLAG_DETACH_FIRST_STEP)) {" in nd
 
 

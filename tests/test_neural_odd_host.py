@@ -229,6 +229,13 @@ def test_workspace_sizes_follow_the_partial_block(lib):
     assert lib.hode_neural_odd_workspace_bytes(_desc(14), L.WS_DOPRI5_FWD) == 0
 
 
+def test_adaptive_workspace_layouts_are_the_recorded_ones(lib):
+    """Totals and tape offsets of the dopri5 workspace at D 5 and 15, to the byte (the table libhode.so's sizes are in)."""
+    import adaptive_layout_table
+    adaptive_layout_table.assert_layouts(lib.hode_neural_odd_workspace_bytes, lib.hode_neural_odd_dopri5_tape_offsets,
+                                         {("NEURAL", 5), ("NEURAL", 15)})
+
+
 # ----------------------------------------------------------------------------------------- 3. sizes nobody serves
 @pytest.mark.parametrize("D", [16, 3])
 def test_error_text_for_a_size_without_a_kernel(D):
