@@ -6,7 +6,9 @@ libhode_flow.so, libhode_mix.so and libhode_blend.so, each with a C ABI header o
 libhode.so; DATA_LIBRARIES holds libhode_datagen.so in the same rows, and TEST_LIBRARIES libhode_probe.so (C ABI
 include/hode_probe.h), which runs the shared device helpers on their own for tests/test_hip_helpers.py and which nothing
 under hode/ loads; SOLVER_LIBRARIES libhode_neural_odd.so (C ABI include/hode_neural_odd.h), the NeuralODE kernels of
-libhode.so instantiated at the odd latent dimensions 5 .. 15, one unit per dimension.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
+libhode.so instantiated at the odd latent dimensions 5 .. 15, one unit per dimension; ROCHE_LIBRARIES libhode_roche_dims.so
+(C ABI include/hode_roche_dims.h), the hybrid Roche kernels at ROCHE_DIMS, the sizes 5 .. 16 libhode.so does not hold, one
+fixed-grid and one dopri5 unit per size.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
 depfile, its flags or this script changed), links each library whose objects are newer than it, and writes
 digest(<library>) next to it as <library>.so.digest; tests and hode/_loader.py compare that stamp with the tree."""
 import argparse
@@ -26,6 +28,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 RK_DIMS = (4, 6, 8, 12, 20)
 DP_DIMS = (4, 6, 8, 12)
 NEURAL_ODD_DIMS = (5, 7, 9, 11, 13, 15)  # csrc/neural_odd/hode_neural_odd_dim.hip; the even ones are in libhode.so
+ROCHE_DIMS = (5, 7, 9, 10, 11, 13, 14, 15, 16)  # csrc/roche_dims/: the hybrid decoder beside RK_DIMS / DP_DIMS
 LSTM_TPWS = (1, 2, 3, 4, 5, 6, 8, 10)   # padded hidden sizes 16 * TPW (csrc/hode_lstm_tpw.hip)
 # per-unit flags (measured on MI355X)
 # -fno-slp-vectorize on the split kernels: packed-fp32 pairing costs more v_mov than it saves (step 0.228 -> 0.207 ms)
@@ -107,8 +110,28 @@ SOLVER_LIBRARIES = {lib.name: lib for lib in (
 )}
 
 
+def _roche_dims_units():
+    d = os.path.join(CSRC, "roche_dims")
+    return [("hode_roche_dims", os.path.join(d, "hode_roche_dims.hip"), []),
+            # the dopri5 entries: libhode.so's unit compiled for this library (its checks, layout and attempt loop, once)
+            ("hode_roche_dims_dopri5", os.path.join(CSRC, "hode_dopri5.hip"), ["-DHODE_ROCHE_DIMS_UNIT"])] + \
+        [("hode_roche_dims_rk_d%d" % n, os.path.join(d, "hode_roche_dims_rk_dim.hip"), ["-DHODE_DIM=%d" % n]) for n in ROCHE_DIMS] + \
+        [("hode_roche_dims_dp_d%d" % n, os.path.join(d, "hode_roche_dims_dp_dim.hip"), ["-DHODE_DIM=%d" % n]) for n in ROCHE_DIMS]
+
+
+#: the hybrid Roche kernels at the sizes libhode.so does not hold, same rows; a table of its own because a test pins the one
+#: name of SOLVER_LIBRARIES.  `extra` lists every file of csrc/ the units include or compile from outside `src_dir`.
+ROCHE_LIBRARIES = {lib.name: lib for lib in (
+    Library("libhode_roche_dims.so", PKG + "/csrc/roche_dims", "include/hode_roche_dims.h",
+            tuple(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_lanes.hpp", "hode_roche.hpp", "hode_host.hpp",
+                                               "hode_rk_host.hpp", "hode_rk_kernels.hpp", "hode_dopri5_kernels.hpp",
+                                               "hode_adaptive_host.hpp", "hode_error_state.hpp", "hode_dopri5.hip"))
+            + ("include/hode.h",), _roche_dims_units),
+)}
+
+
 def _library(name):
-    for table in (LIBRARIES, DATA_LIBRARIES, TEST_LIBRARIES, SOLVER_LIBRARIES):
+    for table in (LIBRARIES, DATA_LIBRARIES, TEST_LIBRARIES, SOLVER_LIBRARIES, ROCHE_LIBRARIES):
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -116,7 +139,7 @@ def _library(name):
 
 def all_libraries():
     return (list(LIBRARIES.values()) + list(DATA_LIBRARIES.values()) + list(TEST_LIBRARIES.values())
-            + list(SOLVER_LIBRARIES.values()))
+            + list(SOLVER_LIBRARIES.values()) + list(ROCHE_LIBRARIES.values()))
 
 
 OUT = LIBRARIES["libhode.so"].out

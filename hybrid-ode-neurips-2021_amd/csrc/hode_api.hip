@@ -3,71 +3,8 @@
 
 #include "hode_error_state.hpp"  // hode::fail / hip_fail and the message behind hode_last_error_string: defined here, once
 #include "hode_host.hpp"
+#include "hode_rk_host.hpp"  // the lane kernels' host code (grid, layout rule, fold, checks): defined here, once
 #include "hode_roche.hpp"
-
-namespace hode {
-
-// out[j] += sum over waves of partials[w][j].  One wave per output element: lane l adds rows l, l+64, ... in order,
-// then a fixed-shape butterfly folds the 64 lane sums -- the summation tree depends only on (n_waves), so the
-// result is bit-reproducible run to run (no float atomics).
-__global__ __launch_bounds__(64) void fold_partials_kernel(const float* __restrict__ partials, int n_waves, int P,
-                                                           int n_w, int n_b, float* __restrict__ gw,
-                                                           float* __restrict__ gb, float* __restrict__ gth, int need_th) {
-  const int j = blockIdx.x;
-  const int lane = threadIdx.x;
-  float s = 0.f;
-  for (int w = lane; w < n_waves; w += 64) s += partials[(size_t)w * P + j];
-  s = wave_sum(s);
-  if (lane != 0) return;
-  if (j < n_w) {
-    if (gw) gw[j] += s;
-  } else if (j < n_w + n_b) {
-    if (gb) gb[j - n_w] += s;
-  } else if (need_th && gth) {
-    gth[j - n_w - n_b] += s;
-  }
-}
-
-// patients per wave: as many waves as it takes to put one on (almost) every SIMD, then whole rounds of 1024
-int patients_per_wave(int B, int lpp) {
-  const int cap = 64 / lpp;
-  const long long simds = 1024;
-  const long long rounds = (B + simds * cap - 1) / (simds * cap);
-  long long ppw = (B + simds * rounds - 1) / (simds * rounds);
-  if (ppw < 1) ppw = 1;
-  if (ppw > cap) ppw = cap;
-  return (int)ppw;
-}
-int n_waves_for(int B, int lpp) {
-  const int ppw = patients_per_wave(B, lpp);
-  return (B + ppw - 1) / ppw;
-}
-
-// LPP = 4 (a patient per DPP quad, 16 patients per wave) fills the chip at the 10k-patient shape; LPP = 1 has
-// the lowest total instruction count and wins once every SIMD has >= 2 waves without splitting patients
-// (256 CUs x 4 SIMDs x 2 waves x 64 lanes = 131072 patients).
-int choose_lpp(const hode_solve_desc* d) {
-  const int M = d->latent_dim - 4;
-  const bool can4 = M > 0 && M % 4 == 0;
-  if (d->lanes_per_patient == 1) return 1;
-  if (d->lanes_per_patient == 4) return can4 ? 4 : 1;
-  if (!can4) return 1;
-  return d->batch >= 131072 ? 1 : 4;
-}
-
-int n_partials(const hode_solve_desc* d) {
-  const int M = d->latent_dim - 4;
-  return M * d->latent_dim + M + kNTheta;
-}
-
-
-int launch_fold_partials(const float* partials, int n_waves, int P, int n_w, int n_b, float* gw, float* gb, float* gth,
-                         int need_th, hipStream_t s) {
-  hipLaunchKernelGGL(fold_partials_kernel, dim3(P), dim3(64), 0, s, partials, n_waves, P, n_w, n_b, gw, gb, gth, need_th);
-  return hip_fail(hipGetLastError(), "fold_partials launch");
-}
-
-}  // namespace hode
 
 namespace {
 
@@ -75,18 +12,11 @@ using hode::choose_lpp;
 using hode::n_partials;
 using hode::n_waves_for;
 
+using hode::check_rk;
 using hode::RkArgs;
 using hode::RkLaunch;
 
-RkArgs make_args(const hode_solve_desc* d) {
-  RkArgs a{};
-  a.t = d->t; a.y0 = d->y0; a.dosage = d->dosage; a.dose_times = d->dose_times; a.theta = d->theta;
-  a.w1 = d->w1; a.b1 = d->b1; a.h = d->h; a.grad_h = d->grad_h; a.grad_y0 = d->grad_y0;
-  a.partials = (float*)d->workspace; a.status = d->status;
-  a.B = d->batch; a.T = d->n_times; a.K = d->n_dose; a.perturb = d->perturb;
-  a.ppw = hode::patients_per_wave(d->batch, choose_lpp(d));
-  return a;
-}
+RkArgs make_args(const hode_solve_desc* d) { return hode::rk_make_args(d, choose_lpp(d)); }
 
 // lanes_per_patient == 16 selects the MFMA layout (hode_rk_mf.hip) where it exists for the dimension
 bool use_mf(const hode_solve_desc* d) {
@@ -130,29 +60,6 @@ int dispatch_dim(const hode_solve_desc* d, bool bwd, hipStream_t s) {
     case 20: return hode::rk_dispatch_d20(L, a, s);
   }
   return hode::fail(HODE_E_UNSUPPORTED, "latent_dim %d has no compiled kernel (have 4, 6, 8, 12, 20)", d->latent_dim);
-}
-
-int check_rk(const hode_solve_desc* d, bool bwd) {
-  if (!d) return hode::fail(HODE_E_NULL, "descriptor is NULL");
-  if (d->struct_size != sizeof(hode_solve_desc))
-    return hode::fail(HODE_E_SIZE, "struct_size %u != %zu (ABI mismatch)", d->struct_size, sizeof(hode_solve_desc));
-  if (d->rhs_kind != HODE_RHS_ROCHE && d->rhs_kind != HODE_RHS_ROCHE_ABLATE)
-    return hode::fail(HODE_E_UNSUPPORTED, "rhs_kind %d is not handled by the fixed-grid Roche kernels", d->rhs_kind);
-  if (d->method < HODE_METHOD_EULER || d->method > HODE_METHOD_RK4_38)
-    return hode::fail(HODE_E_UNSUPPORTED, "unknown fixed-grid method %d", d->method);
-  if (d->batch <= 0 || d->n_times <= 0 || d->latent_dim < 4 || d->n_dose < 0)
-    return hode::fail(HODE_E_SIZE, "bad sizes: batch=%d n_times=%d latent_dim=%d n_dose=%d", d->batch, d->n_times,
-                      d->latent_dim, d->n_dose);
-  if (!d->t || !d->y0 || !d->dosage || !d->theta || !d->h || (d->n_dose > 0 && !d->dose_times))
-    return hode::fail(HODE_E_NULL, "t / y0 / dosage / dose_times / theta / h must be non-NULL");
-  if (d->latent_dim > 4 && (!d->w1 || !d->b1)) return hode::fail(HODE_E_NULL, "w1 / b1 required when latent_dim > 4");
-  if (bwd && (!d->grad_h || !d->grad_y0)) return hode::fail(HODE_E_NULL, "grad_h / grad_y0 required by the backward");
-  if (d->latent_dim % 4 == 0) {
-    uintptr_t m = (uintptr_t)d->y0 | (uintptr_t)d->h;
-    if (bwd) m |= (uintptr_t)d->grad_h | (uintptr_t)d->grad_y0;
-    if (m & 15) return hode::fail(HODE_E_ALIGN, "y0 / h / grad_h / grad_y0 must be 16-byte aligned");
-  }
-  return 0;
 }
 
 }  // namespace
@@ -218,17 +125,10 @@ extern "C" int hode_rk_bwd(const hode_solve_desc* d, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if ((d->flags & HODE_FLAG_OVERWRITE_GRADS) && !use_split(d, true)) {
     // the split layout's fold stores directly; the other layouts accumulate, so clear the outputs first
-    const size_t M = d->latent_dim - 4;
-    if (d->grad_w1) if (int e = hode::hip_fail(hipMemsetAsync(d->grad_w1, 0, M * d->latent_dim * sizeof(float), s), "grad_w1 clear")) return e;
-    if (d->grad_b1) if (int e = hode::hip_fail(hipMemsetAsync(d->grad_b1, 0, M * sizeof(float), s), "grad_b1 clear")) return e;
-    if (d->grad_theta) if (int e = hode::hip_fail(hipMemsetAsync(d->grad_theta, 0, hode::kNTheta * sizeof(float), s), "grad_theta clear")) return e;
+    if (int e = hode::rk_clear_grads(d, s)) return e;
   }
   if (int e = dispatch_dim(d, true, s)) return e;
   if (use_split(d, true) || use_mf(d)) return 0;  // these layouts fold their own partials
   if (d->flags & HODE_FLAG_SKIP_FOLD) return 0;
-  const int M = d->latent_dim - 4;
-  const int P = n_partials(d);
-  const int nw = n_waves_for(d->batch, choose_lpp(d));
-  return hode::launch_fold_partials((const float*)d->workspace, nw, P, M * d->latent_dim, M, d->grad_w1, d->grad_b1,
-                                    d->grad_theta, d->need_theta_grad, s);
+  return hode::rk_fold(d, choose_lpp(d), s);
 }

@@ -1,10 +1,27 @@
 // C-ABI entry points hode_dopri5_fwd / hode_dopri5_bwd (include/hode.h): checks, the Roche kernels' arguments and launches.
 // The workspace carving, the chunk policy and the attempt loop are hode_adaptive_host.hpp's, shared with the NeuralODE.
+//
+// This unit is compiled twice, so that the checks, the layout, the arguments and the attempt loop below exist once: as it
+// is for libhode.so, and with -DHODE_ROCHE_DIMS_UNIT for libhode_roche_dims.so (include/hode_roche_dims.h), where the
+// entries are hode_roche_dims_dopri5_*, the table of sizes is that library's, its refusals come first and there is no
+// NeuralODE to hand over to.  (A header would serve as well, but tests/test_kernel_variant_coverage.py reads the Hill
+// read-back out of this file.)
 #include <stdlib.h>
 #include <string.h>
 
 #include "hode_adaptive_host.hpp"
 #include "hode_dopri5_kernels.hpp"
+
+#ifdef HODE_ROCHE_DIMS_UNIT
+#include "roche_dims/hode_roche_dims.hpp"
+#define HODE_DP_ENTRY(name) hode_roche_dims_##name
+#define HODE_DP_DOMAIN(d) if (int e_ = hode::roche_dims_check_domain(d)) return e_;
+constexpr bool kHasNeural = false;
+#else
+#define HODE_DP_ENTRY(name) hode_##name
+#define HODE_DP_DOMAIN(d)
+constexpr bool kHasNeural = true;
+#endif
 
 namespace {
 
@@ -63,6 +80,14 @@ DpArgs dp_args(const hode_solve_desc* d, const AdaptiveLayout& L) {
 }
 
 int dp_dispatch_dim(const hode_solve_desc* d, const DpLaunch& L, const DpArgs& a, hipStream_t s) {
+#ifdef HODE_ROCHE_DIMS_UNIT
+  switch (d->latent_dim) {
+#define HODE_ROCHE_DIMS_CASE(n) case n: return hode::roche_dims_dp_dispatch_d##n(L, a, s);
+    HODE_ROCHE_DIMS(HODE_ROCHE_DIMS_CASE)
+#undef HODE_ROCHE_DIMS_CASE
+  }
+  return hode::roche_dims_check_domain(d);  // names the sizes
+#else
   switch (d->latent_dim) {
     case 4: return hode::dp_dispatch_d4(L, a, s);
     case 6: return hode::dp_dispatch_d6(L, a, s);
@@ -70,9 +95,10 @@ int dp_dispatch_dim(const hode_solve_desc* d, const DpLaunch& L, const DpArgs& a
     case 12: return hode::dp_dispatch_d12(L, a, s);
   }
   return hode::fail(HODE_E_UNSUPPORTED, "dopri5: latent_dim %d has no compiled kernel (have 4, 6, 8, 12)", d->latent_dim);
+#endif
 }
 
-bool is_neural(const hode_solve_desc* d) { return d && d->struct_size == sizeof(hode_solve_desc) && d->rhs_kind == HODE_RHS_NEURAL; }
+bool is_neural(const hode_solve_desc* d) { return kHasNeural && d && d->struct_size == sizeof(hode_solve_desc) && d->rhs_kind == HODE_RHS_NEURAL; }
 
 // argument checks shared by both rhs families
 int check_common(const hode_solve_desc* d, bool bwd) {
@@ -111,14 +137,21 @@ int check_dp(const hode_solve_desc* d, bool bwd) {
 
 }  // namespace
 
+#ifdef HODE_ROCHE_DIMS_UNIT
+size_t hode::roche_dims_dopri5_workspace_bytes(const hode_solve_desc* d) { return dp_layout(d).total; }
+#else
 extern "C" size_t hode_dopri5_workspace_bytes(const hode_solve_desc* d) {
   return is_neural(d) ? hode::neural_dopri5_workspace_bytes(d) : dp_layout(d).total;
 }
+#endif
 
-extern "C" int hode_dopri5_fwd(const hode_solve_desc* d, void* stream) {
-  if (is_neural(d)) {
-    if (int e = check_common(d, false)) return e;
-    return hode::neural_dopri5(d, false, (hipStream_t)stream);
+extern "C" int HODE_DP_ENTRY(dopri5_fwd)(const hode_solve_desc* d, void* stream) {
+  HODE_DP_DOMAIN(d)
+  if constexpr (kHasNeural) {
+    if (is_neural(d)) {
+      if (int e = check_common(d, false)) return e;
+      return hode::neural_dopri5(d, false, (hipStream_t)stream);
+    }
   }
   if (int e = check_dp(d, false)) return e;
   hipStream_t s = (hipStream_t)stream;
@@ -189,10 +222,13 @@ extern "C" int hode_dopri5_fwd(const hode_solve_desc* d, void* stream) {
   return hode::adaptive_report(d, host, s);
 }
 
-extern "C" int hode_dopri5_bwd(const hode_solve_desc* d, void* stream) {
-  if (is_neural(d)) {
-    if (int e = check_common(d, true)) return e;
-    return hode::neural_dopri5(d, true, (hipStream_t)stream);
+extern "C" int HODE_DP_ENTRY(dopri5_bwd)(const hode_solve_desc* d, void* stream) {
+  HODE_DP_DOMAIN(d)
+  if constexpr (kHasNeural) {
+    if (is_neural(d)) {
+      if (int e = check_common(d, true)) return e;
+      return hode::neural_dopri5(d, true, (hipStream_t)stream);
+    }
   }
   if (int e = check_dp(d, true)) return e;
   hipStream_t s = (hipStream_t)stream;
@@ -221,10 +257,13 @@ extern "C" int hode_dopri5_bwd(const hode_solve_desc* d, void* stream) {
                                     d->grad_b1, d->grad_theta, d->need_theta_grad, s);
 }
 
-extern "C" int hode_dopri5_tape_offsets(const hode_solve_desc* d, size_t* out5) {
+extern "C" int HODE_DP_ENTRY(dopri5_tape_offsets)(const hode_solve_desc* d, size_t* out5) {
   if (!d || !out5) return hode::fail(HODE_E_NULL, "descriptor / out5 is NULL");
   if (d->struct_size != sizeof(hode_solve_desc)) return hode::fail(HODE_E_SIZE, "struct_size mismatch");
-  if (is_neural(d)) return hode::neural_dopri5_tape_offsets(d, out5);
+  HODE_DP_DOMAIN(d)
+  if constexpr (kHasNeural) {
+    if (is_neural(d)) return hode::neural_dopri5_tape_offsets(d, out5);
+  }
   hode::adaptive_tape_offsets(dp_layout(d), out5);
   return 0;
 }

@@ -55,6 +55,28 @@ struct StageTimes {
   }
 };
 
+// Ragged quad layout (LPP = 4, D % 4 != 0): a (D,) row is only 4-byte aligned, so the quad stores it as dwords, lane q the
+// elements q, q + 4, ... (a quad's stores are consecutive).  Every other instantiation keeps store_vec's chunks.
+template <int D, int LPP>
+constexpr bool kDwordRows = LPP == 4 && D % 4 != 0;
+
+template <int D, int I>
+HODE_DEV float elem_or(const float (&v)[D], float other) {
+  if constexpr (I < D) return v[I];
+  else return other;
+}
+
+// elements C .. C + 3 of the row, one per lane of the quad (template recursion: every register index is a constant)
+template <int D, int C = 0>
+HODE_DEV void store_dwords(float* __restrict__ p, const float (&v)[D], int q, bool live) {
+  float x = v[C];
+  x = (q == 1) ? elem_or<D, C + 1>(v, x) : x;
+  x = (q == 2) ? elem_or<D, C + 2>(v, x) : x;
+  x = (q == 3) ? elem_or<D, C + 3>(v, x) : x;
+  if (live && C + q < D) p[C + q] = x;
+  if constexpr (C + 4 < D) store_dwords<D, C + 4>(p, v, q, live);
+}
+
 // ------------------------------------------------------------------------------------------------ forward
 template <int D, int LPP, int METHOD, bool ABLATE, bool HILL2, bool K1>
 HODE_DEV void rk_fwd_body(const RkArgs& a) {
@@ -70,7 +92,8 @@ HODE_DEV void rk_fwd_body(const RkArgs& a) {
   load_vec<D>(a.y0 + (size_t)lm.p * D, y);
   const size_t row = (size_t)a.B * D;
   float* hp = a.h + (size_t)lm.p * D;
-  store_vec<D, LPP>(hp, y, lm.q, lm.live);
+  if constexpr (kDwordRows<D, LPP>) store_dwords<D>(hp, y, lm.q, lm.live);
+  else store_vec<D, LPP>(hp, y, lm.q, lm.live);
 
   float own[MR];
   for (int n = 0; n + 1 < a.T; ++n) {
@@ -105,7 +128,8 @@ HODE_DEV void rk_fwd_body(const RkArgs& a) {
       for (int i = 0; i < D; ++i) y[i] = __builtin_fmaf((k1[i] + 3.0f * (k2[i] + k3[i])) + k4[i], w, y[i]);
     }
     hp += row;
-    store_vec<D, LPP>(hp, y, lm.q, lm.live);
+    if constexpr (kDwordRows<D, LPP>) store_dwords<D>(hp, y, lm.q, lm.live);
+    else store_vec<D, LPP>(hp, y, lm.q, lm.live);
   }
   if (a.status) {
     bool bad = false;
@@ -266,22 +290,25 @@ HODE_DEV void rk_bwd_body(const RkArgs& a) {
     }
   }
   if (a.T == 1) { /* lam already = grad_h[0] */ }
-  store_vec<D, LPP>(a.grad_y0 + (size_t)lm.p * D, lam, lm.q, lm.live);
+  if constexpr (kDwordRows<D, LPP>) store_dwords<D>(a.grad_y0 + (size_t)lm.p * D, lam, lm.q, lm.live);
+  else store_vec<D, LPP>(a.grad_y0 + (size_t)lm.p * D, lam, lm.q, lm.live);
 
   // ---- fold the per-lane parameter gradients over the patients of this wave, one partial row per wave
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   float* out = a.partials + (size_t)wave * n_partials<D, LPP>();
   if constexpr (M > 0) {
+    constexpr bool kRagged = Ml::kRagged;  // then a padding slot (row >= M) is not written: its index lies in the bias / theta part
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
+      const bool mine = lane < LPP && (!kRagged || lane * MR + r < M);
 #pragma unroll
       for (int i = 0; i < D; ++i) {
         const float s = (LPP == 4) ? wave_sum_stride4(acc.dw[r][i]) : wave_sum(acc.dw[r][i]);
-        if (lane < LPP) out[(lane * MR + r) * D + i] = s;
+        if (mine) out[(lane * MR + r) * D + i] = s;
       }
       const float sb = (LPP == 4) ? wave_sum_stride4(acc.db[r]) : wave_sum(acc.db[r]);
-      if (lane < LPP) out[M * D + lane * MR + r] = sb;
+      if (mine) out[M * D + lane * MR + r] = sb;
     }
   }
 #pragma unroll
@@ -345,6 +372,14 @@ int dispatch_lpp(const RkLaunch& L, const RkArgs& a, hipStream_t s) {
   if constexpr (D > 4 && (D - 4) % 4 == 0) {
     if (L.lpp == 4) return L.ablate ? dispatch_method<D, 4, true>(L, a, s) : dispatch_method<D, 4, false>(L, a, s);
   }
+  return L.ablate ? dispatch_method<D, 1, true>(L, a, s) : dispatch_method<D, 1, false>(L, a, s);
+}
+
+// the same choice for a library that holds the ragged quad layout: LPP = 4 at every D > 4
+template <int D>
+int dispatch_lpp_ragged(const RkLaunch& L, const RkArgs& a, hipStream_t s) {
+  static_assert(D > 4, "the quad layout splits the learned block");
+  if (L.lpp == 4) return L.ablate ? dispatch_method<D, 4, true>(L, a, s) : dispatch_method<D, 4, false>(L, a, s);
   return L.ablate ? dispatch_method<D, 1, true>(L, a, s) : dispatch_method<D, 1, false>(L, a, s);
 }
 

@@ -5,8 +5,11 @@
 //
 // Lane layout.  A patient is handled by LPP lanes (LPP = 1 or 4).  Every lane of a patient holds the FULL state
 // (D registers) and evaluates the 4 expert components redundantly; the M = D-4 rows of the learned block
-// tanh(W y + b) are split over the lanes (MR = M/LPP rows each, W rows kept in that lane's registers) and
-// all-gathered with DPP quad broadcasts.  With LPP = 4 a wave covers 16 patients, which is what fills the chip
+// tanh(W y + b) are split over the lanes (MR = ceil(M/LPP) rows each, W rows kept in that lane's registers) and
+// all-gathered with DPP quad broadcasts.  Where M % 4 != 0 the quad layout is RAGGED: lane q, slot r is row q*MR + r
+// when that is < M and padding otherwise (zero weights, zero bias: tanh(0) = 0, so a padding slot adds exactly zero
+// everywhere, is never gathered and never read from or written to memory); the D columns of the VJP's transposed
+// product are split ceil(D/4) per lane in the same way.  All of it is indexed at compile time.  With LPP = 4 a wave covers 16 patients, which is what fills the chip
 // at the 10k-patient shape; with LPP = 1 a wave covers 64 patients and the total instruction count is lowest.
 #pragma once
 #include "hode_common.hpp"
@@ -31,7 +34,8 @@ HODE_DEV RocheTheta load_theta(const float* __restrict__ th, bool ablate) {
 template <int D, int LPP>
 struct MlSlice {
   static constexpr int M = D - 4;
-  static constexpr int MR = (M / LPP) > 0 ? (M / LPP) : 1;
+  static constexpr int MR = M > 0 ? (M + LPP - 1) / LPP : 1;
+  static constexpr bool kRagged = M > 0 && M % LPP != 0;  // some (lane, slot) pairs are padding
   float w[MR][D];
   float b[MR];
   HODE_DEV void load(const float* __restrict__ W, const float* __restrict__ bias, int q) {
@@ -39,9 +43,17 @@ struct MlSlice {
 #pragma unroll
       for (int r = 0; r < MR; ++r) {
         const int row = q * MR + r;
+        if constexpr (!kRagged) {
 #pragma unroll
-        for (int i = 0; i < D; ++i) w[r][i] = W[row * D + i];
-        b[r] = bias[row];
+          for (int i = 0; i < D; ++i) w[r][i] = W[row * D + i];
+          b[r] = bias[row];
+        } else {  // a padding slot reads row 0 (in bounds) and keeps zeros
+          const bool ok = row < M;
+          const int rr = ok ? row : 0;
+#pragma unroll
+          for (int i = 0; i < D; ++i) w[r][i] = ok ? W[rr * D + i] : 0.f;
+          b[r] = ok ? bias[rr] : 0.f;
+        }
       }
     }
   }
@@ -52,16 +64,22 @@ struct MlSlice {
 template <int D, int LPP>
 struct MlColSlice {
   static constexpr int M = D - 4;
-  static constexpr int DC = (LPP > 1 && M > 0) ? D / LPP : 1;
+  static constexpr int DC = (LPP > 1 && M > 0) ? (D + LPP - 1) / LPP : 1;
   static constexpr int MM = (LPP > 1 && M > 0) ? M : 1;
   float wt[MM][DC];
   HODE_DEV void load(const float* __restrict__ W, int q) {
     if constexpr (LPP > 1 && M > 0) {
-      static_assert(D % LPP == 0, "quad layout needs D % 4 == 0");
 #pragma unroll
       for (int j = 0; j < M; ++j)
 #pragma unroll
-        for (int c = 0; c < DC; ++c) wt[j][c] = W[j * D + q * DC + c];
+        for (int c = 0; c < DC; ++c) {
+          if constexpr (D % LPP == 0) {
+            wt[j][c] = W[j * D + q * DC + c];
+          } else {  // ragged: a padding column reads column 0 (in bounds) and keeps zero
+            const int col = q * DC + c;
+            wt[j][c] = col < D ? W[j * D + col] : 0.f;
+          }
+        }
     }
   }
 };
@@ -88,11 +106,11 @@ HODE_DEV void gather_rows(const float (&own)[MlSlice<D, LPP>::MR], float (&k)[D]
     } else {
       static_assert(LPP == 4, "only quad layout implemented");
 #pragma unroll
-      for (int r = 0; r < MR; ++r) {
+      for (int r = 0; r < MR; ++r) {  // (the bounds only bite in the ragged layout: padding slots are not gathered)
         k[4 + 0 * MR + r] = quad_bcast<0>(own[r]);
-        k[4 + 1 * MR + r] = quad_bcast<1>(own[r]);
-        k[4 + 2 * MR + r] = quad_bcast<2>(own[r]);
-        k[4 + 3 * MR + r] = quad_bcast<3>(own[r]);
+        if (4 + 1 * MR + r < D) k[4 + 1 * MR + r] = quad_bcast<1>(own[r]);
+        if (4 + 2 * MR + r < D) k[4 + 2 * MR + r] = quad_bcast<2>(own[r]);
+        if (4 + 3 * MR + r < D) k[4 + 3 * MR + r] = quad_bcast<3>(own[r]);
       }
     }
   }
@@ -211,9 +229,19 @@ HODE_DEV void roche_vjp(const RocheTheta& th, const MlSlice<D, LPP>& ml, const M
   // ---- learned block: u_r = g_r (1 - s_r^2)
   if constexpr (D > 4) {
     float u[MR];
+    // ragged quad layout: the cotangent of the learned block, zero-padded to LPP * MR slots (a padding slot picks zero)
+    float gpad[MlSlice<D, LPP>::kRagged ? LPP * MR : 1];
+    if constexpr (MlSlice<D, LPP>::kRagged) {
+#pragma unroll
+      for (int j = 0; j < LPP * MR; ++j) gpad[j] = 0.f;
+#pragma unroll
+      for (int j = 0; j < M; ++j) gpad[j] = g[4 + j];
+    }
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
-      const float gr = pick_own<LPP, MR, D>(g, 4, r, q);
+      float gr;
+      if constexpr (MlSlice<D, LPP>::kRagged) gr = pick_own<LPP, MR, LPP * MR>(gpad, 0, r, q);
+      else gr = pick_own<LPP, MR, D>(g, 4, r, q);
       u[r] = gr * __builtin_fmaf(-own_s[r], own_s[r], 1.0f);
       acc.db[r] += u[r];
 #pragma unroll
@@ -233,9 +261,9 @@ HODE_DEV void roche_vjp(const RocheTheta& th, const MlSlice<D, LPP>& ml, const M
 #pragma unroll
       for (int r = 0; r < MR; ++r) {
         uf[0 * MR + r] = quad_bcast<0>(u[r]);
-        uf[1 * MR + r] = quad_bcast<1>(u[r]);
-        uf[2 * MR + r] = quad_bcast<2>(u[r]);
-        uf[3 * MR + r] = quad_bcast<3>(u[r]);
+        if (1 * MR + r < M) uf[1 * MR + r] = quad_bcast<1>(u[r]);
+        if (2 * MR + r < M) uf[2 * MR + r] = quad_bcast<2>(u[r]);
+        if (3 * MR + r < M) uf[3 * MR + r] = quad_bcast<3>(u[r]);
       }
 #pragma unroll
       for (int c = 0; c < DC; ++c) {
@@ -243,9 +271,9 @@ HODE_DEV void roche_vjp(const RocheTheta& th, const MlSlice<D, LPP>& ml, const M
 #pragma unroll
         for (int j = 0; j < M; ++j) p = __builtin_fmaf(mc.wt[j][c], uf[j], p);
         a[0 * DC + c] = quad_bcast<0>(p);
-        a[1 * DC + c] = quad_bcast<1>(p);
-        a[2 * DC + c] = quad_bcast<2>(p);
-        a[3 * DC + c] = quad_bcast<3>(p);
+        if (1 * DC + c < D) a[1 * DC + c] = quad_bcast<1>(p);
+        if (2 * DC + c < D) a[2 * DC + c] = quad_bcast<2>(p);
+        if (3 * DC + c < D) a[3 * DC + c] = quad_bcast<3>(p);
       }
     }
   } else {

@@ -7,6 +7,7 @@ calling it without the library or with CPU tensors raises.
 """
 
 from ._lib import HodeConfigError, HodeError, lib, library_path  # noqa: F401
+from ._roche_dims_lib import roche_solver_library  # noqa: F401  (loads nothing until it is asked for a size of its library)
 from .solver import odeint, roche_solve  # noqa: F401
 
-__all__ = ["odeint", "roche_solve", "lib", "library_path", "HodeError", "HodeConfigError"]
+__all__ = ["odeint", "roche_solve", "roche_solver_library", "lib", "library_path", "HodeError", "HodeConfigError"]

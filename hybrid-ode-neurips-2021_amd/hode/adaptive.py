@@ -14,6 +14,7 @@ import torch
 
 from . import _lib as L
 from ._neural_odd_lib import DIMS as NEURAL_ODD_DIMS, neural_solver_library
+from ._roche_dims_lib import roche_solver_library
 from .solver import _f32c, _ptr, _require_gpu, _stream
 
 #: last forward's step statistics (diagnostics; mirrors what torchdiffeq exposes through nfe counters)
@@ -32,7 +33,12 @@ def read_tape():
         raise L.HodeConfigError("hode.adaptive.read_tape: no workspace kept (set keep_workspace = True before the solve)")
     ws, d, n_acc = _last_ws
     off = (C.c_size_t * 5)()
-    lib = neural_solver_library(d.latent_dim) if d.rhs_kind == L.RHS_NEURAL else L.lib()
+    if d.rhs_kind == L.RHS_NEURAL:
+        lib = neural_solver_library(d.latent_dim)
+    elif d.rhs_kind in (L.RHS_ROCHE, L.RHS_ROCHE_ABLATE):
+        lib = roche_solver_library(d.latent_dim)
+    else:
+        lib = L.lib()
     L.check(lib.hode_dopri5_tape_offsets(d, off), "hode_dopri5_tape_offsets")
     raw = ws.cpu().numpy()
     import numpy as np
@@ -58,9 +64,9 @@ class _RocheDopri5(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y0, theta, w, b, t, dosage, dose_times, rtol, atol, ablate, lanes, max_steps, detach_first_step,
-                grad_enabled=True):
+                grad_enabled=True, library=None):
         _require_gpu(y0, theta, t, dosage, dose_times)
-        lib = L.lib()
+        lib = ctx.library = L.lib() if library is None else library
         B, D = y0.shape
         T = t.numel()
         y0c, thc, tc = _f32c(y0), _f32c(theta), _f32c(t)
@@ -120,7 +126,7 @@ class _RocheDopri5(torch.autograd.Function):
     def backward(ctx, grad_h):
         h, thc, wc, bc, tc, dosc, dtc, y0c, ws = ctx.saved_tensors
         rtol, atol, ablate, lanes, has_w, steps, n_accepted, detach_first = ctx.meta
-        lib = L.lib()
+        lib = ctx.library
         T, B, D = h.shape
         gh = _f32c(grad_h)
         need_th = bool(ctx.needs_input_grad[1])
@@ -145,19 +151,20 @@ class _RocheDopri5(torch.autograd.Function):
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
         with torch.cuda.device(h.device):
             L.check(lib.hode_dopri5_bwd(d, _stream()), "hode_dopri5_bwd")
-        return gy0, (gth if need_th else None), gw, gb, None, None, None, None, None, None, None, None, None, None
+        return gy0, (gth if need_th else None), gw, gb, None, None, None, None, None, None, None, None, None, None, None
 
 
 def roche_dopri5(y0, theta, w, b, t, dosage, dose_times, rtol=1e-7, atol=1e-9, ablate=False, lanes_per_patient=0,
-                 max_steps=0, detach_first_step=False):
-    """Adaptive solve of the Roche rhs; returns h (T, B, D).  Arguments as ``hode.roche_solve``.
+                 max_steps=0, detach_first_step=False, library=None):
+    """Adaptive solve of the Roche rhs; returns h (T, B, D).  Arguments as ``hode.roche_solve``, ``library`` included:
+    ``None`` is libhode.so (D in 4, 6, 8, 12), ``hode.roche_solver_library(D)`` the library that holds D.
 
     The backward differentiates Hairer's first step size like torchdiffeq's graph does (reference model.py:1116 +
     training_utils.py:50); ``detach_first_step=True`` treats it as a constant (``HODE_FLAG_DETACH_FIRST_STEP``)."""
     if dose_times.dim() != 2:
         dose_times = dose_times.reshape(y0.shape[0], -1)
     return _RocheDopri5.apply(y0, theta, w, b, t, dosage, dose_times.to(torch.float32), rtol, atol, bool(ablate),
-                              int(lanes_per_patient), int(max_steps), bool(detach_first_step), torch.is_grad_enabled())
+                              int(lanes_per_patient), int(max_steps), bool(detach_first_step), torch.is_grad_enabled(), library)
 
 
 class _NeuralDopri5(torch.autograd.Function):

@@ -76,9 +76,9 @@ class _RocheFixedGrid(torch.autograd.Function):
     Gradients for y0, theta, w, b; none for t, dosage, dose_times (their .grad stays None)."""
 
     @staticmethod
-    def forward(ctx, y0, theta, w, b, t, dosage, dose_times, method, ablate, perturb, lanes, check_finite):
+    def forward(ctx, y0, theta, w, b, t, dosage, dose_times, method, ablate, perturb, lanes, check_finite, library=None):
         _require_gpu(y0, theta, t, dosage, dose_times)
-        lib = L.lib()
+        lib = ctx.library = L.lib() if library is None else library
         B, D = y0.shape
         T = t.numel()
         y0c, thc, tc = _f32c(y0), _f32c(theta), _f32c(t)
@@ -117,7 +117,7 @@ class _RocheFixedGrid(torch.autograd.Function):
     def backward(ctx, grad_h):
         h, thc, wc, bc, tc, dosc, dtc = ctx.saved_tensors
         method, ablate, perturb, lanes, has_w = ctx.meta
-        lib = L.lib()
+        lib = ctx.library
         T, B, D = h.shape
         gh = _f32c(grad_h)
         need_th = bool(ctx.needs_input_grad[1])
@@ -143,22 +143,27 @@ class _RocheFixedGrid(torch.autograd.Function):
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
         with torch.cuda.device(h.device):
             L.check(lib.hode_rk_bwd(d, _stream()), "hode_rk_bwd")
-        return gy0, (gth if need_th else None), gw, gb, None, None, None, None, None, None, None, None
+        return gy0, (gth if need_th else None), gw, gb, None, None, None, None, None, None, None, None, None
 
 
 def roche_solve(y0, theta, w, b, t, dosage, dose_times, method="rk4", ablate=False, perturb=False,
-                lanes_per_patient=0, check_finite=False):
+                lanes_per_patient=0, check_finite=False, library=None):
     """Functional form: integrate the Roche rhs over grid ``t`` from ``y0``; returns h (T, B, D).
 
     ``theta`` is the [16] packed vector of expert constants (``pack_theta``), ``w``/``b`` the ``ml_net.0`` weight
     (D-4, D) and bias (D-4,) or ``None`` when D == 4, ``dosage`` (B,), ``dose_times`` (B, K) fp32.
+
+    ``library`` is the kernel library to call: ``None`` is libhode.so, which holds D in 4, 6, 8, 12, 20 and refuses every
+    other size; ``hode.roche_solver_library(D)`` answers with the library that holds D (libhode_roche_dims.so for 5, 7, 9,
+    10, 11, 13, 14, 15, 16).  The choice is the caller's (``model.RocheODE`` makes it), so that this function alone keeps
+    behaving as it did.
     """
     if method not in L.METHODS:
         raise ValueError("hode.roche_solve: method %r is not a fixed-grid method" % (method,))
     if dose_times.dim() != 2:
         dose_times = dose_times.reshape(y0.shape[0], -1)
     return _RocheFixedGrid.apply(y0, theta, w, b, t, dosage, dose_times.to(torch.float32), L.METHODS[method], bool(ablate),
-                                 bool(perturb), int(lanes_per_patient), bool(check_finite))
+                                 bool(perturb), int(lanes_per_patient), bool(check_finite), library)
 
 
 def odeint(func, y0, t, *, rtol=1e-7, atol=1e-9, method=None, options=None):

@@ -308,17 +308,24 @@ class RocheODE(nn.Module):
             raise RuntimeError("RocheODE: call set_action(a) before integrating")
         w = self.ml_net[0].weight if self.expanded else None
         b = self.ml_net[0].bias if self.expanded else None
+        from hode import _roche_dims_lib as RL
+        held = RL.DIMS + (RL.LIBHODE_DP_DIMS if method == "dopri5" else RL.LIBHODE_RK_DIMS)
+        if self.latent_dim not in held:
+            raise hode.HodeConfigError("hode: RocheODE with method=%r is compiled for latent dimensions %s (got %d); "
+                                       "there is no torch-eager path in the product"
+                                       % (method, RL.sizes_text(method == "dopri5"), self.latent_dim))
+        library = RL.roche_solver_library(self.latent_dim)
         if method == "dopri5":
             from hode import adaptive
             return adaptive.roche_dopri5(y0, self.theta_vector(), w, b, t, self.dosage, self.times, rtol=rtol, atol=atol,
-                                         ablate=self.ablate)
+                                         ablate=self.ablate, library=library)
         from hode import substep
         perturb = bool(options.pop("perturb", False))
         theta = self.theta_vector()
         return substep.solve_with_step_size(
             lambda grid: hode.roche_solve(y0, theta, w, b, grid, self.dosage, self.times, method=method, ablate=self.ablate,
                                           perturb=perturb, lanes_per_patient=self.lanes_per_patient,
-                                          check_finite=self.check_finite),
+                                          check_finite=self.check_finite, library=library),
             t, options.pop("step_size", None))
 
 
