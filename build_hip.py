@@ -8,7 +8,9 @@ include/hode_probe.h), which runs the shared device helpers on their own for tes
 under hode/ loads; SOLVER_LIBRARIES libhode_neural_odd.so (C ABI include/hode_neural_odd.h), the NeuralODE kernels of
 libhode.so instantiated at the odd latent dimensions 5 .. 15, one unit per dimension; ROCHE_LIBRARIES libhode_roche_dims.so
 (C ABI include/hode_roche_dims.h), the hybrid Roche kernels at ROCHE_DIMS, the sizes 5 .. 16 libhode.so does not hold, one
-fixed-grid and one dopri5 unit per size.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
+fixed-grid and one dopri5 unit per size; REAL_LIBRARIES libhode_real_dims.so (C ABI include/hode_real_dims.h), the real-data
+hybrid rhs on the matrix cores at the latent sizes 5 .. 20 with the size as a runtime argument, one unit per hidden-tile
+count.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
 depfile, its flags or this script changed), links each library whose objects are newer than it, and writes
 digest(<library>) next to it as <library>.so.digest; tests and hode/_loader.py compare that stamp with the tree."""
 import argparse
@@ -29,6 +31,7 @@ RK_DIMS = (4, 6, 8, 12, 20)
 DP_DIMS = (4, 6, 8, 12)
 NEURAL_ODD_DIMS = (5, 7, 9, 11, 13, 15)  # csrc/neural_odd/hode_neural_odd_dim.hip; the even ones are in libhode.so
 ROCHE_DIMS = (5, 7, 9, 10, 11, 13, 14, 15, 16)  # csrc/roche_dims/: the hybrid decoder beside RK_DIMS / DP_DIMS
+REAL_DIMS_HTS = (1, 2, 3, 4)  # csrc/real_dims/hode_real_dims_ht.hip: hidden tiles of 16 (hidden_dim 1 .. 64)
 LSTM_TPWS = (1, 2, 3, 4, 5, 6, 8, 10)   # padded hidden sizes 16 * TPW (csrc/hode_lstm_tpw.hip)
 # per-unit flags (measured on MI355X)
 # -fno-slp-vectorize on the split kernels: packed-fp32 pairing costs more v_mov than it saves (step 0.228 -> 0.207 ms)
@@ -130,8 +133,25 @@ ROCHE_LIBRARIES = {lib.name: lib for lib in (
 )}
 
 
+def _real_dims_units():
+    d = os.path.join(CSRC, "real_dims")
+    # -Wno-unused-function: hode_rk_host.hpp is included for the partial fold; its Roche argument helpers are not called here
+    return [("hode_real_dims", os.path.join(d, "hode_real_dims.hip"), ["-Wno-unused-function"])] + \
+        [("hode_real_dims_ht%d" % n, os.path.join(d, "hode_real_dims_ht.hip"), ["-DHODE_REAL_DIMS_HT=%d" % n]) for n in REAL_DIMS_HTS]
+
+
+#: the real-data hybrid rhs at the latent sizes libhode.so does not hold, same rows; a table of its own because tests pin the
+#: names of the other tables.  `extra` lists every file of csrc/ the units include from outside `src_dir`.
+REAL_LIBRARIES = {lib.name: lib for lib in (
+    Library("libhode_real_dims.so", PKG + "/csrc/real_dims", "include/hode_real_dims.h",
+            tuple(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_roche.hpp", "hode_host.hpp", "hode_rk_host.hpp",
+                                               "hode_error_state.hpp", "hode_real_args.hpp", "hode_real_mf.hpp"))
+            + ("include/hode.h",), _real_dims_units),
+)}
+
+
 def _library(name):
-    for table in (LIBRARIES, DATA_LIBRARIES, TEST_LIBRARIES, SOLVER_LIBRARIES, ROCHE_LIBRARIES):
+    for table in (LIBRARIES, DATA_LIBRARIES, TEST_LIBRARIES, SOLVER_LIBRARIES, ROCHE_LIBRARIES, REAL_LIBRARIES):
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -139,7 +159,7 @@ def _library(name):
 
 def all_libraries():
     return (list(LIBRARIES.values()) + list(DATA_LIBRARIES.values()) + list(TEST_LIBRARIES.values())
-            + list(SOLVER_LIBRARIES.values()) + list(ROCHE_LIBRARIES.values()))
+            + list(SOLVER_LIBRARIES.values()) + list(ROCHE_LIBRARIES.values()) + list(REAL_LIBRARIES.values()))
 
 
 OUT = LIBRARIES["libhode.so"].out

@@ -1,7 +1,7 @@
-// The error state of a library that spans several translation units (libhode.so, libhode_neural_odd.so): the thread-local
+// The error state of a library that spans several translation units (libhode.so, libhode_neural_odd.so and the like): the thread-local
 // message its *_last_error_string returns, and the definitions of hode::fail / hode::hip_fail that hode_host.hpp declares
 // for every unit.  The two functions have external linkage, so this header is included by exactly ONE unit per library
-// (hode_api.hip, neural_odd/hode_neural_odd.hip); each library thereby keeps a message of its own.  The single-unit side
+// (hode_api.hip, neural_odd/hode_neural_odd.hip, roche_dims/hode_roche_dims.hip, real_dims/hode_real_dims.hip); each library thereby keeps a message of its own.  The single-unit side
 // libraries use hode_side_error.hpp, whose copy has internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,7 +1,8 @@
 // Host code of the fixed-grid Roche lane kernels (hode_rk_kernels.hpp) that every library holding them needs: the grid
 // shape, the layout rule, the per-wave partial row and its fold, the kernel arguments and the argument checks.  The
 // functions hode_host.hpp declares have external linkage, so this header is included by exactly ONE unit per library
-// (hode_api.hip of libhode.so, roche_dims/hode_roche_dims.hip of libhode_roche_dims.so), like hode_error_state.hpp.
+// (hode_api.hip of libhode.so, roche_dims/hode_roche_dims.hip of libhode_roche_dims.so, and real_dims/hode_real_dims.hip of
+// libhode_real_dims.so, which needs the partial fold alone), like hode_error_state.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

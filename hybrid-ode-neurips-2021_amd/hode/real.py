@@ -1,4 +1,5 @@
-"""Fixed-grid solve of the real-data hybrid ODE (reference ``RocheODEReal``, ``model.py:570-657``) on the gfx950 kernels.
+"""Fixed-grid solve of the real-data hybrid ODE (reference ``RocheODEReal``, ``model.py:570-657``) on the gfx950 kernels:
+libhode.so at the latent sizes 4 and 20, libhode_real_dims.so (matrix cores, on-chip weight gradients) at 5 .. 19.
 
 The backward kernel returns ``grad_y0`` and the gradients of the three scalars, and tapes the operands of every linear
 layer's weight gradient; they are contracted here with batched BLAS GEMMs and returned as one flat gradient matching
@@ -9,6 +10,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
+from . import _real_dims_lib as RD
 from .solver import _f32c, _require_gpu, _stream
 
 _STAGES = {L.METHOD_EULER: 1, L.METHOD_MIDPOINT: 2, L.METHOD_RK4_38: 4}
@@ -27,9 +29,8 @@ class _RealFixedGrid(torch.autograd.Function):
     """Gradients for y0, theta, wflat; none for t and the action table act (their .grad stays None)."""
 
     @staticmethod
-    def forward(ctx, y0, theta, wflat, t, act, method, perturb, hidden, lanes):
+    def forward(ctx, y0, theta, wflat, t, act, method, perturb, hidden, lanes, lib):
         _require_gpu(y0, theta, wflat, t, act)
-        lib = L.lib()
         y0c, thc, wc, tc, ac = _f32c(y0), _f32c(theta), _f32c(wflat), _f32c(t), _f32c(act)
         B, D = y0c.shape
         M = D - 4
@@ -43,14 +44,13 @@ class _RealFixedGrid(torch.autograd.Function):
         with torch.cuda.device(y0.device):
             L.check(lib.hode_rk_fwd(d, _stream()), "hode_rk_fwd[real]")
         ctx.save_for_backward(h, thc, wc, tc, ac)
-        ctx.meta = (method, int(perturb), int(hidden), lanes)
+        ctx.meta = (method, int(perturb), int(hidden), lanes, lib)
         return h
 
     @staticmethod
     def backward(ctx, grad_h):
         h, thc, wc, tc, ac = ctx.saved_tensors
-        method, perturb, H, lanes = ctx.meta
-        lib = L.lib()
+        method, perturb, H, lanes, lib = ctx.meta
         T, B, D = h.shape
         gh = _f32c(grad_h)
         gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)
@@ -58,9 +58,10 @@ class _RealFixedGrid(torch.autograd.Function):
         d = _desc(h[0], tc, ac, thc, wc, h, method, perturb, H)
         d.lanes_per_patient = lanes
         d.grad_h, d.grad_y0, d.grad_theta = gh.data_ptr(), gy0.data_ptr(), gth.data_ptr()
-        # matrix-core kernels (D = 20, hidden <= 64): the weight gradients are accumulated on chip into this flat buffer;
-        # the lane-per-patient kernels (lanes_per_patient = 1, D = 4, hidden > 64) tape the GEMM operands for contract_tape
-        onchip = D == 20 and H <= 64 and lanes != 1
+        # matrix-core kernels (D = 20, hidden <= 64; the side library at every size it serves): the weight gradients are
+        # accumulated on chip into this flat buffer; the lane-per-patient kernels (lanes_per_patient = 1, D = 4,
+        # hidden > 64) tape the GEMM operands for contract_tape
+        onchip = RD.is_side_library(lib) or (D == 20 and H <= 64 and lanes != 1)
         if onchip:
             gw = torch.zeros_like(wc)
             d.grad_w1 = gw.data_ptr()
@@ -70,8 +71,8 @@ class _RealFixedGrid(torch.autograd.Function):
         with torch.cuda.device(h.device):
             L.check(lib.hode_rk_bwd(d, _stream()), "hode_rk_bwd[real]")
         if onchip:
-            return gy0, gth[:3].clone(), gw, None, None, None, None, None, None
-        return gy0, gth[:3].clone(), contract_tape(ws, T, B, D, H, method), None, None, None, None, None, None
+            return gy0, gth[:3].clone(), gw, None, None, None, None, None, None, None
+        return gy0, gth[:3].clone(), contract_tape(ws, T, B, D, H, method), None, None, None, None, None, None, None
 
 
 def contract_tape(ws, T, B, D, H, method):
@@ -115,10 +116,18 @@ def contract_tape(ws, T, B, D, H, method):
     return torch.cat(parts)
 
 
-def real_solve(y0, theta, wflat, t, act, hidden, method="midpoint", perturb=True, lanes_per_patient=0):
+def real_solve(y0, theta, wflat, t, act, hidden, method="midpoint", perturb=True, lanes_per_patient=0, library=None):
     """h (T, B, D).  ``theta`` = (k_immunity, kel, kel2); ``wflat`` = all weights in creation order; ``act`` (Ta, B) doses.
     ``lanes_per_patient`` forces a kernel family (tuning / tests): 1 = one patient per lane, 16 = matrix cores where they
-    exist; 0 = the library chooses."""
+    exist; 0 = the library chooses.  ``library`` is the kernel library to call; None chooses by latent size
+    (``real_solver_library``: libhode_real_dims.so for D = 5 .. 19, libhode.so otherwise)."""
     if method not in L.METHODS:
         raise L.HodeConfigError("hode: the real-data rhs is built for the fixed-grid methods (euler, midpoint, rk4); got %r" % (method,))
-    return _RealFixedGrid.apply(y0, theta, wflat, t, act, L.METHODS[method], bool(perturb), int(hidden), int(lanes_per_patient))
+    D, hidden, lanes = int(y0.shape[-1]), int(hidden), int(lanes_per_patient)
+    if library is None and D in RD.DIMS and (not 1 <= hidden <= RD.MAX_HIDDEN or lanes == 1):
+        # refused here, before a library is loaded or anything is launched, with the sizes of both libraries
+        raise L.HodeConfigError("hode: the real-data hybrid rhs has no kernel for latent_dim %d with hidden_dim %d, lanes_per_patient %d; "
+                                "have %s" % (D, hidden, lanes, RD.sizes_text()))
+    if library is None:
+        library = RD.real_solver_library(D)
+    return _RealFixedGrid.apply(y0, theta, wflat, t, act, L.METHODS[method], bool(perturb), hidden, lanes, library)

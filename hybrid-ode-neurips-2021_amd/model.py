@@ -556,8 +556,9 @@ class RocheODEReal(nn.Module):
         wflat, perturb = self.flat_weights(), bool(options.pop("perturb", False))
         # more than one action column: the reference's sum over dims (0, 2) adds them all into the dose (see the class docstring)
         dose = self.dosage[..., 0] if self.dosage.shape[-1] == 1 else self.dosage.sum(-1)
+        # which library serves this latent size (libhode.so at 4 and 20, libhode_real_dims.so at 5 .. 19) is real_solve's choice
         return substep.solve_with_step_size(
-            lambda grid: real.real_solve(y0, theta, wflat, grid, dose, self.hidden_dim, method=method, perturb=perturb),
+            lambda grid: real.real_solve(y0, theta, wflat, grid, dose, self.hidden_dim, method=method, perturb=perturb, library=None),
             t, step_size)
 
 
