@@ -10,7 +10,8 @@ libhode.so instantiated at the odd latent dimensions 5 .. 15, one unit per dimen
 (C ABI include/hode_roche_dims.h), the hybrid Roche kernels at ROCHE_DIMS, the sizes 5 .. 16 libhode.so does not hold, one
 fixed-grid and one dopri5 unit per size; REAL_LIBRARIES libhode_real_dims.so (C ABI include/hode_real_dims.h), the real-data
 hybrid rhs on the matrix cores at the latent sizes 5 .. 20 with the size as a runtime argument, one unit per hidden-tile
-count.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
+count; SEQUENCE_LIBRARIES libhode_lstm_seq.so (C ABI include/hode_lstm_seq.h), the LSTM window kernels of libhode.so
+under their all-steps policy (the hidden state of every step), the LSTM units compiled a second time.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
 depfile, its flags or this script changed), links each library whose objects are newer than it, and writes
 digest(<library>) next to it as <library>.so.digest; tests and hode/_loader.py compare that stamp with the tree."""
 import argparse
@@ -90,6 +91,7 @@ DATA_LIBRARIES = {lib.name: lib for lib in (
 #: header of csrc/ the unit includes, so that its digest follows an edit of a helper.
 TEST_LIBRARIES = {lib.name: lib for lib in (
     _side("probe", *(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_lanes.hpp", "hode_lstm_kernels.hpp",
+                                                  "hode_lstm_fwd_body.hpp", "hode_lstm_bwd_body.hpp",
                                                   "hode_neural_mf.hpp", "hode_neural_args.hpp", "hode_roche.hpp",
                                                   "hode_host.hpp")), "include/hode.h"),
 )}
@@ -150,8 +152,28 @@ REAL_LIBRARIES = {lib.name: lib for lib in (
 )}
 
 
+def _lstm_seq_units():
+    # libhode.so's LSTM units compiled for this library (its checks, geometry, packing and launch code, once)
+    seq = ["-DHODE_LSTM_SEQ_UNIT"]
+    return [("hode_lstm_seq", os.path.join(CSRC, "lstm_seq", "hode_lstm_seq.hip"), []),
+            ("hode_lstm_seq_host", os.path.join(CSRC, "hode_lstm.hip"), seq)] + \
+        [("hode_lstm_seq_tpw%d" % n, os.path.join(CSRC, "hode_lstm_tpw.hip"), seq + ["-DHODE_LSTM_TPW=%d" % n]) for n in LSTM_TPWS]
+
+
+#: the LSTM kernels with the hidden state of every step as output, same rows; a table of its own because tests pin the names
+#: of the other tables.  `extra` lists every file of csrc/ the units include or compile from outside `src_dir`.
+SEQUENCE_LIBRARIES = {lib.name: lib for lib in (
+    Library("libhode_lstm_seq.so", PKG + "/csrc/lstm_seq", "include/hode_lstm_seq.h",
+            tuple(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_host.hpp", "hode_error_state.hpp",
+                                               "hode_lstm_kernels.hpp", "hode_lstm_fwd_body.hpp", "hode_lstm_bwd_body.hpp",
+                                               "hode_lstm.hip", "hode_lstm_tpw.hip"))
+            + ("include/hode.h",), _lstm_seq_units),
+)}
+
+
 def _library(name):
-    for table in (LIBRARIES, DATA_LIBRARIES, TEST_LIBRARIES, SOLVER_LIBRARIES, ROCHE_LIBRARIES, REAL_LIBRARIES):
+    for table in (LIBRARIES, DATA_LIBRARIES, TEST_LIBRARIES, SOLVER_LIBRARIES, ROCHE_LIBRARIES, REAL_LIBRARIES,
+                  SEQUENCE_LIBRARIES):
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -159,7 +181,8 @@ def _library(name):
 
 def all_libraries():
     return (list(LIBRARIES.values()) + list(DATA_LIBRARIES.values()) + list(TEST_LIBRARIES.values())
-            + list(SOLVER_LIBRARIES.values()) + list(ROCHE_LIBRARIES.values()) + list(REAL_LIBRARIES.values()))
+            + list(SOLVER_LIBRARIES.values()) + list(ROCHE_LIBRARIES.values()) + list(REAL_LIBRARIES.values())
+            + list(SEQUENCE_LIBRARIES.values()))
 
 
 OUT = LIBRARIES["libhode.so"].out

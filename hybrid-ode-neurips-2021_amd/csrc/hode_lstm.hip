@@ -1,7 +1,19 @@
 // Host side of the masked LSTM encoder kernels (csrc/hode_lstm_kernels.hpp): weight packing, launch geometry, the
 // hode_lstm_* entry points of include/hode.h.  The kernels themselves are instantiated per padded hidden size in
 // csrc/hode_lstm_tpw.hip.
+//
+// Compiled twice: as it is for libhode.so, and with -DHODE_LSTM_SEQ_UNIT for libhode_lstm_seq.so (include/hode_lstm_seq.h),
+// where the entries are hode_lstm_seq_* and the per-size units launch the all-steps kernels: h_out and grad_h_out are
+// [T][B][H] there.  The checks, the geometry, the packing and the workspace layout are the same code.
 #include "hode_lstm_kernels.hpp"
+
+#ifdef HODE_LSTM_SEQ_UNIT
+#define HODE_LSTM_ENTRY(name) hode_lstm_seq_##name
+#define HODE_LSTM_ENTRY_TEXT(name) "hode_lstm_seq_" #name
+#else
+#define HODE_LSTM_ENTRY(name) hode_lstm_##name
+#define HODE_LSTM_ENTRY_TEXT(name) "hode_lstm_" #name
+#endif
 
 namespace hode {
 
@@ -147,7 +159,7 @@ int launch_fwd(const LstmGeom& G, const LstmArgs& a, hipStream_t s) {
 }  // namespace
 
 // workspace: [packed Wcat (bias row included) | packed W_hh^T (tape runs only) | tape (tape runs only)]
-extern "C" size_t hode_lstm_workspace_bytes(const hode_lstm_desc* d) {
+extern "C" size_t HODE_LSTM_ENTRY(workspace_bytes)(const hode_lstm_desc* d) {
   LstmGeom G;
   if (!d || d->struct_size != sizeof(hode_lstm_desc) || lstm_geom(d, &G, d->save_tape != 0)) return 0;
   size_t n = align256(G.wp_floats * 4);
@@ -155,11 +167,11 @@ extern "C" size_t hode_lstm_workspace_bytes(const hode_lstm_desc* d) {
   return n;
 }
 
-extern "C" int hode_lstm_fwd(const hode_lstm_desc* d, void* stream) {
+extern "C" int HODE_LSTM_ENTRY(fwd)(const hode_lstm_desc* d, void* stream) {
   if (int e = check_lstm(d)) return e;
   LstmGeom G;
   if (int e = lstm_geom(d, &G, d->save_tape != 0)) return e;
-  const size_t need = hode_lstm_workspace_bytes(d);
+  const size_t need = HODE_LSTM_ENTRY(workspace_bytes)(d);
   if (!d->workspace || d->workspace_bytes < need)
     return hode::fail(HODE_E_WORKSPACE, "workspace %zu B < required %zu B", d->workspace_bytes, need);
   hipStream_t s = (hipStream_t)stream;
@@ -198,14 +210,14 @@ int launch_bwd(const LstmGeom& G, const hode::LstmBwdArgs& a, hipStream_t s) {
 // [grad_w_ih | grad_w_hh | grad_b | 0]: dG is read once, the N dimension fills the BLAS tile (244 of 256 instead of 80 of
 // 128 and 162 of 256: 3.4 -> 2.4 ms) and the bias sum needs no pass of its own.  (Writing x*mask from this kernel was
 // tried: +0.55 ms here against 0.15 ms for the caller's element-wise kernel.)
-extern "C" int hode_lstm_bwd(const hode_lstm_desc* d, void* stream) {
+extern "C" int HODE_LSTM_ENTRY(bwd)(const hode_lstm_desc* d, void* stream) {
   if (int e = check_lstm(d)) return e;
-  if (!d->save_tape) return hode::fail(HODE_E_UNSUPPORTED, "hode_lstm_bwd needs the tape of a forward run with save_tape = 1");
+  if (!d->save_tape) return hode::fail(HODE_E_UNSUPPORTED, HODE_LSTM_ENTRY_TEXT(bwd) " needs the tape of a forward run with save_tape = 1");
   if (!d->grad_h_out || !d->grad_gates || !d->h_prev)
     return hode::fail(HODE_E_NULL, "grad_h_out / grad_gates / h_prev must be non-NULL");
   LstmGeom G;
   if (int e = lstm_geom(d, &G, true)) return e;
-  const size_t need = hode_lstm_workspace_bytes(d);
+  const size_t need = HODE_LSTM_ENTRY(workspace_bytes)(d);
   if (!d->workspace || d->workspace_bytes < need)
     return hode::fail(HODE_E_WORKSPACE, "workspace %zu B < required %zu B", d->workspace_bytes, need);
   if (G.lds_bwd_bytes > 160 * 1024)
@@ -260,7 +272,7 @@ __global__ __launch_bounds__(256) void lstm_fill_operand_kernel(const float* __r
 }
 }  // namespace hode
 
-extern "C" int hode_lstm_fill_operand(const hode_lstm_desc* d, void* stream) {
+extern "C" int HODE_LSTM_ENTRY(fill_operand)(const hode_lstm_desc* d, void* stream) {
   if (int e = check_lstm(d)) return e;
   if (!d->h_prev) return hode::fail(HODE_E_NULL, "h_prev must be non-NULL");
   const int obs = d->obs_dim, W = (d->input_dim + d->hidden_dim + 1 + 3) / 4 * 4;

@@ -1,6 +1,8 @@
 // Instantiates the LSTM window / BPTT kernels for ONE padded hidden size Hp = 16 * HODE_LSTM_TPW (the backward runs 4
 // waves x TPW unit tiles; the forward TPW <= 5: 4 waves x TPW tiles, above: 8 waves x TPW/2 tiles -- two waves per SIMD, all
 // accumulators in the VGPR file).  Compiled once per -DHODE_LSTM_TPW=<n> so the sizes build in parallel (build_hip.py).
+// Compiled a second time with -DHODE_LSTM_SEQ_UNIT for libhode_lstm_seq.so (include/hode_lstm_seq.h): the same launch
+// code then launches the all-steps kernels lstm_seq_fwd_kernel / lstm_seq_bwd_kernel, and only those.
 #include "hode_lstm_kernels.hpp"
 
 #ifndef HODE_LSTM_TPW
@@ -9,6 +11,14 @@
 
 #define HODE_CAT_(a, b) a##b
 #define HODE_CAT(a, b) HODE_CAT_(a, b)
+
+#ifdef HODE_LSTM_SEQ_UNIT
+#define HODE_LSTM_FWD_KERNEL hode::lstm_seq_fwd_kernel
+#define HODE_LSTM_BWD_KERNEL hode::lstm_seq_bwd_kernel
+#else
+#define HODE_LSTM_FWD_KERNEL hode::lstm_fwd_kernel
+#define HODE_LSTM_BWD_KERNEL hode::lstm_bwd_kernel
+#endif
 
 namespace {
 
@@ -22,11 +32,11 @@ static_assert(kFwdTPW * kFwdNW == kTPW * 4, "forward geometry must cover the pad
 
 template <int NT, bool VEC4>
 int launch_fwd_vec(const LstmGeom& G, const LstmArgs& a, hipStream_t s) {
-  if (int e = hode::hip_fail(hipFuncSetAttribute((const void*)hode::lstm_fwd_kernel<NT, kFwdTPW, kFwdNW, VEC4>,
+  if (int e = hode::hip_fail(hipFuncSetAttribute((const void*)HODE_LSTM_FWD_KERNEL<NT, kFwdTPW, kFwdNW, VEC4>,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)G.lds_bytes),
                              "hipFuncSetAttribute(MaxDynamicSharedMemorySize)"))
     return e;
-  hipLaunchKernelGGL((hode::lstm_fwd_kernel<NT, kFwdTPW, kFwdNW, VEC4>), dim3(G.nblk), dim3(64 * kFwdNW), G.lds_bytes, s, a);
+  hipLaunchKernelGGL((HODE_LSTM_FWD_KERNEL<NT, kFwdTPW, kFwdNW, VEC4>), dim3(G.nblk), dim3(64 * kFwdNW), G.lds_bytes, s, a);
   return hode::hip_fail(hipGetLastError(), "lstm_fwd launch");
 }
 
@@ -37,11 +47,11 @@ int launch_fwd_one(const LstmGeom& G, const LstmArgs& a, hipStream_t s) {
 
 template <int NT, bool FLAT>
 int launch_bwd_flat(const LstmGeom& G, const hode::LstmBwdArgs& a, hipStream_t s) {
-  if (int e = hode::hip_fail(hipFuncSetAttribute((const void*)hode::lstm_bwd_kernel<NT, kTPW, FLAT>,
+  if (int e = hode::hip_fail(hipFuncSetAttribute((const void*)HODE_LSTM_BWD_KERNEL<NT, kTPW, FLAT>,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)G.lds_bwd_bytes),
                              "hipFuncSetAttribute(MaxDynamicSharedMemorySize)"))
     return e;
-  hipLaunchKernelGGL((hode::lstm_bwd_kernel<NT, kTPW, FLAT>), dim3(G.nblk), dim3(256), G.lds_bwd_bytes, s, a);
+  hipLaunchKernelGGL((HODE_LSTM_BWD_KERNEL<NT, kTPW, FLAT>), dim3(G.nblk), dim3(256), G.lds_bwd_bytes, s, a);
   return hode::hip_fail(hipGetLastError(), "lstm_bwd launch");
 }
 

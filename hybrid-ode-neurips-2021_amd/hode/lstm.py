@@ -1,7 +1,8 @@
 """Masked LSTM encoder on the gfx950 matrix cores (``hode_lstm_fwd`` / ``hode_lstm_bwd``).
 
 Replaces the T single-step ``nn.LSTM`` calls of reference ``EncoderLSTM.forward`` (``model.py:420-422``) together with
-the ``cat([x, a]) * cat([mask, 1])`` that feeds them.
+the ``cat([x, a]) * cat([mask, 1])`` that feeds them.  ``lstm_sequence`` is the same LSTM with the hidden state of every
+step as its output (libhode_lstm_seq.so: reference ``LSTMBaseline``, ``EncoderLSTMReal(output_all=True)``).
 """
 
 from __future__ import annotations
@@ -9,6 +10,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
+from . import _lstm_seq_lib as SL
 from .solver import _f32c, _ptr, _require_gpu, _stream
 
 
@@ -114,18 +116,23 @@ def _side_stream(device):
 
 class _LstmEncode(torch.autograd.Function):
     """h_final = LSTM(window); backward = BPTT kernel + one split-K BLAS GEMM over K = T*B for all weight and bias gradients.
-    Gradients for the four LSTM parameters; none for x, a, mask (their .grad stays None)."""
+    Gradients for the four LSTM parameters; none for x, a, mask (their .grad stays None).
+
+    ``all_steps``: the output is h of every step, (T, B, H), row t the state after consuming input row t, and the backward
+    takes a cotangent on every row -- the same entries of libhode_lstm_seq.so (``_lstm_seq_lib.lstm_library``).  Only then
+    is the tape left out when no parameter needs a gradient."""
 
     @staticmethod
-    def forward(ctx, x, a, mask, w_ih, w_hh, b_ih, b_hh, reverse, patient_tiles):
+    def forward(ctx, x, a, mask, w_ih, w_hh, b_ih, b_hh, reverse, patient_tiles, all_steps=False):
         _require_gpu(x, w_ih)
-        lib = L.lib()
+        lib = SL.lstm_library(all_steps)
         xc, ac, mc = _f32c(x), (None if a is None else _f32c(a)), (None if mask is None else _f32c(mask))
         wi, wh, bi, bh = _f32c(w_ih), _f32c(w_hh), _f32c(b_ih), _f32c(b_hh)
-        B, H = xc.shape[1], wh.shape[1]
-        h = torch.empty((B, H), device=x.device, dtype=torch.float32)
+        T, B, H = xc.shape[0], xc.shape[1], wh.shape[1]
+        save_tape = any(ctx.needs_input_grad[3:7]) if all_steps else True
+        h = torch.empty((T, B, H) if all_steps else (B, H), device=x.device, dtype=torch.float32)
         c = torch.empty((B, H), device=x.device, dtype=torch.float32)
-        d = _desc(xc, ac, mc, wi, wh, bi, bh, reverse, True)
+        d = _desc(xc, ac, mc, wi, wh, bi, bh, reverse, save_tape)
         d.patient_tiles, d.h_out, d.c_out = patient_tiles, h.data_ptr(), c.data_ptr()
         nbytes = lib.hode_lstm_workspace_bytes(d)
         if nbytes == 0:
@@ -135,16 +142,16 @@ class _LstmEncode(torch.autograd.Function):
         with torch.cuda.device(x.device), _Span("lstm_fwd"):
             L.check(lib.hode_lstm_fwd(d, _stream()), "hode_lstm_fwd")
         ctx.save_for_backward(xc, ac if ac is not None else xc, mc if mc is not None else xc, wi, wh, bi, bh, ws)
-        ctx.flags = (ac is not None, mc is not None, bool(reverse), patient_tiles)
+        ctx.flags = (ac is not None, mc is not None, bool(reverse), patient_tiles, bool(all_steps))
         return h
 
     @staticmethod
     def backward(ctx, grad_h):
         xc, ac, mc, wi, wh, bi, bh, ws = ctx.saved_tensors
-        has_a, has_m, reverse, patient_tiles = ctx.flags
+        has_a, has_m, reverse, patient_tiles, all_steps = ctx.flags
         ac = ac if has_a else None
         mc = mc if has_m else None
-        lib = L.lib()
+        lib = SL.lstm_library(all_steps)
         T, B, obs = xc.shape
         H = wh.shape[1]
         gh = _f32c(grad_h)
@@ -175,10 +182,20 @@ class _LstmEncode(torch.autograd.Function):
         g_wih = g[:, :I].contiguous()
         g_whh = g[:, I:I + H].contiguous()
         g_b = g[:, I + H].contiguous()
-        return None, None, None, g_wih, g_whh, g_b, g_b.clone(), None, None
+        return None, None, None, g_wih, g_whh, g_b, g_b.clone(), None, None, None
 
 
 def lstm_encode(x, a, mask, w_ih, w_hh, b_ih, b_hh, reverse=True, patient_tiles=0):
     """Differentiable (w.r.t. the four LSTM parameters) final hidden state (B, H) of the masked window LSTM.
     ``patient_tiles`` as in ``lstm_final_state``."""
-    return _LstmEncode.apply(x, a, mask, w_ih, w_hh, b_ih, b_hh, bool(reverse), int(patient_tiles))
+    return _LstmEncode.apply(x, a, mask, w_ih, w_hh, b_ih, b_hh, bool(reverse), int(patient_tiles), False)
+
+
+def lstm_sequence(x, a, mask, w_ih, w_hh, b_ih, b_hh, reverse=False, patient_tiles=0):
+    """Differentiable (w.r.t. the four LSTM parameters) hidden state of EVERY step, (T, B, H), of the masked window LSTM:
+    row t is the state after the step that consumed input row t (``reverse``: the walk is t = T-1 .. 0 and row 0 is the last
+    state).  Arguments as ``lstm_encode``; ``.grad`` of x, a, mask stays None.  Under ``torch.no_grad()``, or when no
+    parameter needs a gradient, the forward writes no tape."""
+    if not torch.is_grad_enabled():
+        w_ih, w_hh, b_ih, b_hh = w_ih.detach(), w_hh.detach(), b_ih.detach(), b_hh.detach()
+    return _LstmEncode.apply(x, a, mask, w_ih, w_hh, b_ih, b_hh, bool(reverse), int(patient_tiles), True)

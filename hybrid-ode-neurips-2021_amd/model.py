@@ -15,6 +15,7 @@ latent ODE is integrated by the gfx950 kernels of ``libhode.so`` (``hode.odeint`
     GRUODECell / DecoderRealBenchmark ("tlstm", "gruode" baselines)         model.py:865-966  (hode.seqdec kernels)
     NeuralODEReal / NeuralODEReal2nd ("neural", "2nd" baselines)           model.py:660-769  (hode.neural_real kernels)
     EncoderPlanarLSTM / VariationalInferenceFlow (planar-flow posterior)   model.py:48-153, 1299-1380 (hode.flow kernels)
+    LSTMBaseline (sequence-to-sequence LSTM forecaster)                    model.py:322-380  (hode.lstm.lstm_sequence)
 
 Out of scope: Sylvester flows (unused by the reference).
 """
@@ -426,7 +427,9 @@ class RocheExpertDecoder(nn.Module):
 
 class EncoderLSTMReal(nn.Module, GaussianReparam):
     """Real-data encoder (model.py:180-242): LSTM over cat(x, a_in, t/max(mask)) with NO input masking, two-layer tanh
-    heads; ``reverse`` flips the window first, ``output_all`` is not used on the hot path (run_real.py passes False)."""
+    heads; ``reverse`` flips the window first.  ``output_all`` returns the two heads at every step of the window,
+    (T, B, output_dim) each, rows in processing order (after the flip when ``reverse``; as in the reference they are not
+    flipped back) -- ``hode.lstm.lstm_sequence``; run_real.py passes False (the final step: ``hode.lstm.lstm_encode``)."""
 
     def __init__(self, input_dim, hidden_dim, output_dim, output_all=False, reverse=True, normalize=True, device=None):
         super().__init__()
@@ -441,15 +444,19 @@ class EncoderLSTMReal(nn.Module, GaussianReparam):
         self.output_all = output_all
 
     def forward(self, x, a, m):
-        if self.output_all:
-            raise hode.HodeConfigError("EncoderLSTMReal(output_all=True) is outside the accelerated path")
         if self.reverse:
             x, a, m = torch.flip(x, [0]), torch.flip(a, [0]), torch.flip(m, [0])
         T, B = m.shape[0], m.shape[1]
         tt = (torch.arange(T, device=x.device, dtype=x.dtype) / m.max()).view(T, 1, 1).expand(T, B, 1)
         x_in = torch.cat([x, a, tt], dim=-1)
         p = self.lstm
-        if x_in.is_cuda:
+        if self.output_all:
+            if x_in.is_cuda:
+                from hode.lstm import lstm_sequence
+                out = lstm_sequence(x_in, None, None, p.weight_ih_l0, p.weight_hh_l0, p.bias_ih_l0, p.bias_hh_l0, reverse=False)
+            else:
+                out = p(x_in)[0]
+        elif x_in.is_cuda:
             from hode.lstm import lstm_encode
             out = lstm_encode(x_in, None, None, p.weight_ih_l0, p.weight_hh_l0, p.bias_ih_l0, p.bias_hh_l0, reverse=False)
         else:
@@ -457,6 +464,51 @@ class EncoderLSTMReal(nn.Module, GaussianReparam):
         if out.is_cuda:
             return _tall_mlp(self.lin, out), _tall_mlp(self.log_var, out)
         return self.lin(out), self.log_var(out)
+
+
+class LSTMBaseline(nn.Module):
+    """Sequence-to-sequence LSTM forecaster for the real-data set (model.py:322-380): an LSTM over cat(x, a) in forward time
+    (the mask is not applied to the inputs, as in the reference), then Linear(H, H+1) / ELU / Linear(H+1, output_dim) on the
+    hidden state of every step; ``loss`` is the masked one-step-ahead SSE.
+
+    HIP tensors: ``hode.lstm.lstm_sequence`` (the window kernel with every step's h as output, the BPTT kernel with a
+    cotangent per step) and ``_tall_mlp`` for the readout; a hidden size above 160 raises ``HodeConfigError``.  CPU tensors
+    (host-logic tests): ``nn.LSTM``."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim, normalize=True, device=None):
+        super().__init__()
+        self.device = get_device() if device is None else device
+        self.hidden_dim = hidden_dim
+        self.normalize = normalize
+        self.output_dim = output_dim
+        self.model_name = "LSTMBaseline"
+        # creation order lstm -> out fixes both the seeded init and the state_dict key order
+        self.lstm = nn.LSTM(input_dim, hidden_dim).to(self.device)
+        self.out = nn.Sequential(nn.Linear(self.hidden_dim, self.hidden_dim + 1, bias=True), nn.ELU(),
+                                 nn.Linear(self.hidden_dim + 1, self.output_dim, bias=True)).to(self.device)
+
+    def forward(self, x, a, mask):
+        if x.dim() == 3 and x.shape[1] == 1:
+            raise RuntimeError("LSTMBaseline: batch size 1 is not supported (the reference's x.squeeze() drops the batch axis)")
+        p = self.lstm
+        if x.is_cuda:
+            from hode.lstm import lstm_sequence
+            out = lstm_sequence(x, a, None, p.weight_ih_l0, p.weight_hh_l0, p.bias_ih_l0, p.bias_hh_l0, reverse=False)
+            return _tall_mlp(self.out, out)
+        out, _ = p(torch.cat([x, a], dim=-1))
+        return self.out(out)
+
+    def loss(self, data):
+        x, a, mask, s = data["measurements"], data["actions"], data["masks"], data["statics"]
+        a_in = torch.cat([a, s], dim=-1)
+        x_hat = self.forward(x, a_in, mask)[:-1]
+        # row t of x_hat predicts x[t + 1]; masked SSE per patient of the batch
+        return torch.sum((x[1:] - x_hat) ** 2 * mask[1:]) / x.shape[1]
+
+    def save(self, path, itr, best_loss):
+        path = path + self.model_name
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        torch.save({"itr": itr, "state_dict": self.state_dict(), "best_loss": best_loss}, path)
 
 
 class RocheODEReal(nn.Module):
