@@ -11,7 +11,9 @@ libhode.so instantiated at the odd latent dimensions 5 .. 15, one unit per dimen
 fixed-grid and one dopri5 unit per size; REAL_LIBRARIES libhode_real_dims.so (C ABI include/hode_real_dims.h), the real-data
 hybrid rhs on the matrix cores at the latent sizes 5 .. 20 with the size as a runtime argument, one unit per hidden-tile
 count; SEQUENCE_LIBRARIES libhode_lstm_seq.so (C ABI include/hode_lstm_seq.h), the LSTM window kernels of libhode.so
-under their all-steps policy (the hidden state of every step), the LSTM units compiled a second time.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
+under their all-steps policy (the hidden state of every step), the LSTM units compiled a second time; STEP_LIBRARIES
+libhode_real_step.so (C ABI include/hode_real_step.h), the one-step-ahead solve of the real-data hybrid rhs (a start state
+per interval), one unit per hidden-tile count.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
 depfile, its flags or this script changed), links each library whose objects are newer than it, and writes
 digest(<library>) next to it as <library>.so.digest; tests and hode/_loader.py compare that stamp with the tree."""
 import argparse
@@ -33,6 +35,7 @@ DP_DIMS = (4, 6, 8, 12)
 NEURAL_ODD_DIMS = (5, 7, 9, 11, 13, 15)  # csrc/neural_odd/hode_neural_odd_dim.hip; the even ones are in libhode.so
 ROCHE_DIMS = (5, 7, 9, 10, 11, 13, 14, 15, 16)  # csrc/roche_dims/: the hybrid decoder beside RK_DIMS / DP_DIMS
 REAL_DIMS_HTS = (1, 2, 3, 4)  # csrc/real_dims/hode_real_dims_ht.hip: hidden tiles of 16 (hidden_dim 1 .. 64)
+REAL_STEP_HTS = (1, 2, 3, 4)  # csrc/real_step/hode_real_step_ht.hip: the same tiles for the one-step-ahead solve
 LSTM_TPWS = (1, 2, 3, 4, 5, 6, 8, 10)   # padded hidden sizes 16 * TPW (csrc/hode_lstm_tpw.hip)
 # per-unit flags (measured on MI355X)
 # -fno-slp-vectorize on the split kernels: packed-fp32 pairing costs more v_mov than it saves (step 0.228 -> 0.207 ms)
@@ -171,9 +174,26 @@ SEQUENCE_LIBRARIES = {lib.name: lib for lib in (
 )}
 
 
+def _real_step_units():
+    d = os.path.join(CSRC, "real_step")
+    # -Wno-unused-function: hode_rk_host.hpp is included for the partial fold; its Roche argument helpers are not called here
+    return [("hode_real_step", os.path.join(d, "hode_real_step.hip"), ["-Wno-unused-function"])] + \
+        [("hode_real_step_ht%d" % n, os.path.join(d, "hode_real_step_ht.hip"), ["-DHODE_REAL_STEP_HT=%d" % n]) for n in REAL_STEP_HTS]
+
+
+#: the one-step-ahead solve of the real-data hybrid rhs, same rows; a table of its own because tests pin the names of the
+#: other tables.  `extra` lists every file of csrc/ the units include from outside `src_dir`.
+STEP_LIBRARIES = {lib.name: lib for lib in (
+    Library("libhode_real_step.so", PKG + "/csrc/real_step", "include/hode_real_step.h",
+            tuple(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_roche.hpp", "hode_host.hpp", "hode_rk_host.hpp",
+                                               "hode_error_state.hpp", "hode_real_args.hpp", "hode_real_mf.hpp"))
+            + ("include/hode.h",), _real_step_units),
+)}
+
+
 def _library(name):
     for table in (LIBRARIES, DATA_LIBRARIES, TEST_LIBRARIES, SOLVER_LIBRARIES, ROCHE_LIBRARIES, REAL_LIBRARIES,
-                  SEQUENCE_LIBRARIES):
+                  SEQUENCE_LIBRARIES, STEP_LIBRARIES):
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -182,7 +202,7 @@ def _library(name):
 def all_libraries():
     return (list(LIBRARIES.values()) + list(DATA_LIBRARIES.values()) + list(TEST_LIBRARIES.values())
             + list(SOLVER_LIBRARIES.values()) + list(ROCHE_LIBRARIES.values()) + list(REAL_LIBRARIES.values())
-            + list(SEQUENCE_LIBRARIES.values()))
+            + list(SEQUENCE_LIBRARIES.values()) + list(STEP_LIBRARIES.values()))
 
 
 OUT = LIBRARIES["libhode.so"].out

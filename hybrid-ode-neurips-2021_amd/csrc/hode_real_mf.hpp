@@ -1,9 +1,10 @@
 // Device code of the real-data hybrid rhs on the matrix cores, shared by the two libraries that hold it: libhode.so
 // (hode_real_mf.hip: D = 20, the GRU block fills its 16-row tile) and libhode_real_dims.so (real_dims/: D = 5 .. 20, a ragged
 // tile with M = D - 4 as a runtime argument).  RealMf is the rhs and its VJP on register-resident weight operands,
-// RealGradAcc the on-chip weight-gradient accumulator, real_grad_fold its fold, real_mf_body the time loop and its discrete
-// adjoint; the kernels of either library are thin __global__ wrappers around the last two.  See hode_real_mf.hip for the
-// recipe.
+// RealGradAcc the on-chip weight-gradient accumulator, real_grad_fold its fold, real_step_fwd / HODE_REAL_STEP_STAGES /
+// HODE_REAL_STEP_CHAIN one solver step and its adjoint, real_mf_body the time loop over them and its discrete adjoint; the kernels
+// of either library are thin __global__ wrappers around the fold and the body.  libhode_real_step.so (real_step/) walks
+// independent intervals with the same pieces.  See hode_real_mf.hip for the recipe.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -318,6 +319,140 @@ HODE_DEV void real_grad_fold(const float* __restrict__ partials, int n_waves, in
   }
 }
 
+// ------------------------------------------------------------------------------------ one solver step, shared pieces
+// What real_mf_body (the chained solve) and csrc/real_step/ (the one-step-ahead solve) both run: the guarded state I/O of a
+// tile, the dose of a stage, the stage arithmetic of one solver step forward, its recomputation for the adjoint and the
+// cotangent chain through the stages.
+constexpr int real_stages(int method) { return method == HODE_METHOD_EULER ? 1 : (method == HODE_METHOD_MIDPOINT ? 2 : 4); }
+
+template <class Tile>
+HODE_DEV void real_load_state(const Tile& tile, int g, const float* src, v4& X, v4& Hs) {  // src -> one patient's D floats
+  X = v4{0.f, 0.f, 0.f, 0.f};
+  if constexpr (Tile::kRagged) {
+    const int M = tile.m();
+    if (g == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) X[r] = src[r];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Hs[r] = 4 * g + r < M ? src[4 + 4 * g + r] : 0.f;
+  } else {
+    if (g == 0) X = *reinterpret_cast<const v4*>(src);
+    Hs = *reinterpret_cast<const v4*>(src + 4 + 4 * g);
+  }
+}
+template <class Tile>
+HODE_DEV void real_store_state(const Tile& tile, int g, float* dst, const v4& X, const v4& Hs) {  // the caller checks `live`
+  if constexpr (Tile::kRagged) {
+    const int M = tile.m();
+    if (g == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dst[r] = X[r];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (4 * g + r < M) dst[4 + 4 * g + r] = Hs[r];
+  } else {
+    if (g == 0) *reinterpret_cast<v4*>(dst) = X;
+    *reinterpret_cast<v4*>(dst + 4 + 4 * g) = Hs;
+  }
+}
+template <class Stage>
+HODE_DEV void real_set_dose(const RealArgs& a, int p, float kel, bool g0, Stage& s, float t) {
+  s.dv = 0.f;
+  s.ddk = 0.f;
+  if (g0) {
+    const DoseK d = real_dose(a, p, t, kel);
+    s.dv = d.v;
+    s.ddk = d.dk;
+  }
+}
+
+// (X, Hs) at st.t0 -> (X, Hs) at st.t1; `s` is the caller's stage scratch, set_dose(stage, t) fills a stage's dose
+template <int METHOD, class Net, class SetDose>
+HODE_DEV void real_step_fwd(const Net& nn, typename Net::Stage& s, const RStageTimes& st, v4& X, v4& Hs, SetDose&& set_dose) {
+  constexpr float c13 = (float)(1.0 / 3.0);
+  const float dt = st.dt;
+  v4 k1H;
+  s.X = X; s.Hs = Hs; set_dose(s, st.t_first);
+  nn.rhs(s, k1H);
+  const v4 k1X = s.KX;
+  if constexpr (METHOD == HODE_METHOD_EULER) {
+    X = X + dt * k1X; Hs = Hs + dt * k1H;
+  } else if constexpr (METHOD == HODE_METHOD_MIDPOINT) {
+    v4 k2H;
+    s.X = X + (0.5f * dt) * k1X; s.Hs = Hs + (0.5f * dt) * k1H; set_dose(s, st.ta);
+    nn.rhs(s, k2H);
+    X = X + dt * s.KX; Hs = Hs + dt * k2H;
+  } else {
+    v4 k2H, k3H, k4H;
+    s.X = X + (dt * k1X) * c13; s.Hs = Hs + (dt * k1H) * c13; set_dose(s, st.ta);
+    nn.rhs(s, k2H);
+    const v4 k2X = s.KX;
+    s.X = X + dt * (k2X - k1X * c13); s.Hs = Hs + dt * (k2H - k1H * c13); set_dose(s, st.tb);
+    nn.rhs(s, k3H);
+    const v4 k3X = s.KX;
+    s.X = X + dt * ((k1X - k2X) + k3X); s.Hs = Hs + dt * ((k1H - k2H) + k3H); set_dose(s, st.t_last);
+    nn.rhs(s, k4H);
+    X = X + ((k1X + 3.0f * (k2X + k3X)) + s.KX) * (dt * 0.125f);
+    Hs = Hs + ((k1H + 3.0f * (k2H + k3H)) + k4H) * (dt * 0.125f);
+  }
+}
+
+// The stages of the step from (X, Hs) over `st`, kept for the VJPs: s[q] and kH[q] of stage q (arrays of real_stages(METHOD)
+// entries).  A macro, not a function: as an inlined function the same statements compile to another instruction schedule in
+// the chained kernels, whose device code is held fixed (profiles/real_step_device_code_diff.txt).
+constexpr float kRealThird = (float)(1.0 / 3.0);
+#define HODE_REAL_STEP_STAGES(METHOD, nn, s, kH, st, X, Hs, set_dose)                                                        \
+  s[0].X = X; s[0].Hs = Hs; set_dose(s[0], st.t_first);                                                                      \
+  nn.rhs(s[0], kH[0]);                                                                                                       \
+  if constexpr (METHOD == HODE_METHOD_MIDPOINT) {                                                                            \
+    s[1].X = X + (0.5f * st.dt) * s[0].KX; s[1].Hs = Hs + (0.5f * st.dt) * kH[0]; set_dose(s[1], st.ta);                     \
+    nn.rhs(s[1], kH[1]);                                                                                                     \
+  } else if constexpr (METHOD == HODE_METHOD_RK4_38) {                                                                       \
+    s[1].X = X + (st.dt * s[0].KX) * kRealThird; s[1].Hs = Hs + (st.dt * kH[0]) * kRealThird; set_dose(s[1], st.ta);         \
+    nn.rhs(s[1], kH[1]);                                                                                                     \
+    s[2].X = X + st.dt * (s[1].KX - s[0].KX * kRealThird); s[2].Hs = Hs + st.dt * (kH[1] - kH[0] * kRealThird);              \
+    set_dose(s[2], st.tb);                                                                                                   \
+    nn.rhs(s[2], kH[2]);                                                                                                     \
+    s[3].X = X + st.dt * ((s[0].KX - s[1].KX) + s[2].KX); s[3].Hs = Hs + st.dt * ((kH[0] - kH[1]) + kH[2]);                  \
+    set_dose(s[3], st.t_last);                                                                                               \
+    nn.rhs(s[3], kH[3]);                                                                                                     \
+  }
+
+// (lamX, lamH) at the end of the step of length dt -> at its start; vjp(q, gX, gH, aX, aH) is the VJP of stage q.  Declares aX
+// and aH in the enclosing scope.  A macro for the reason given above.
+#define HODE_REAL_STEP_CHAIN(METHOD, dt, lamX, lamH, vjp)                                                                     \
+  v4 aX, aH;                                                                                                                  \
+  if constexpr (METHOD == HODE_METHOD_EULER) {                                                                                \
+    vjp(0, dt * lamX, dt * lamH, aX, aH);                                                                                     \
+    lamX = lamX + aX; lamH = lamH + aH;                                                                                       \
+  } else if constexpr (METHOD == HODE_METHOD_MIDPOINT) {                                                                      \
+    vjp(1, dt * lamX, dt * lamH, aX, aH);                                                                                     \
+    lamX = lamX + aX; lamH = lamH + aH;                                                                                       \
+    const v4 gX = (0.5f * dt) * aX, gH = (0.5f * dt) * aH;                                                                    \
+    vjp(0, gX, gH, aX, aH);                                                                                                   \
+    lamX = lamX + aX; lamH = lamH + aH;                                                                                       \
+  } else {                                                                                                                    \
+    const float w1 = dt * 0.125f, w3 = dt * 0.375f;                                                                           \
+    vjp(3, w1 * lamX, w1 * lamH, aX, aH);                                                                                     \
+    v4 daX = dt * aX, daH = dt * aH;                                                                                          \
+    v4 g1X = w1 * lamX + daX, g1H = w1 * lamH + daH;                                                                          \
+    v4 g2X = w3 * lamX - daX, g2H = w3 * lamH - daH;                                                                          \
+    const v4 gX = w3 * lamX + daX, gH = w3 * lamH + daH;                                                                      \
+    lamX = lamX + aX; lamH = lamH + aH;                                                                                       \
+    vjp(2, gX, gH, aX, aH);                                                                                                   \
+    daX = dt * aX; daH = dt * aH;                                                                                             \
+    g2X = g2X + daX; g2H = g2H + daH;                                                                                         \
+    g1X = g1X - kRealThird * daX; g1H = g1H - kRealThird * daH;                                                               \
+    lamX = lamX + aX; lamH = lamH + aH;                                                                                       \
+    vjp(1, g2X, g2H, aX, aH);                                                                                                 \
+    g1X = g1X + kRealThird * (dt * aX); g1H = g1H + kRealThird * (dt * aH);                                                   \
+    lamX = lamX + aX; lamH = lamH + aH;                                                                                       \
+    vjp(0, g1X, g1H, aX, aH);                                                                                                 \
+    lamX = lamX + aX; lamH = lamH + aH;                                                                                       \
+  }
+
 // ONCHIP (backward): weight gradients accumulated by the wave (RealGradAcc), one partial block per wave in a.tape;
 // otherwise the GEMM operands are taped for the caller (contract of the lane-per-patient kernels).
 // `tile` says how the M = D - 4 GRU states sit in the 16-row H tile: RealTileFull (M = 16, rows of 20 floats, float4 I/O) or
@@ -330,8 +465,7 @@ HODE_DEV void real_mf_body(const RealArgs& a, const Tile tile, float* lds) {
   typedef typename Net::Stage Stage;
   constexpr int NT2 = 2 * HT;
   const int M = tile.m(), D = M + 4;
-  constexpr int NS = METHOD == HODE_METHOD_EULER ? 1 : (METHOD == HODE_METHOD_MIDPOINT ? 2 : 4);
-  constexpr float c13 = (float)(1.0 / 3.0);
+  constexpr int NS = real_stages(METHOD);
   const int lane = threadIdx.x;
   Net nn;
   nn.load(a, tile, lane);
@@ -348,44 +482,11 @@ HODE_DEV void real_mf_body(const RealArgs& a, const Tile tile, float* lds) {
   if constexpr (BWD && ONCHIP) acc.init(lds);
   if (g0) real_dose_table(a, p, nn.kel);  // each lane reads back only its own column
 
-  auto load_state = [&](const float* src, v4& X, v4& Hs) {  // src -> this patient's D floats
-    X = v4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (Tile::kRagged) {
-      if (g0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) X[r] = src[r];
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Hs[r] = 4 * g + r < M ? src[4 + 4 * g + r] : 0.f;
-    } else {
-      if (g0) X = *reinterpret_cast<const v4*>(src);
-      Hs = *reinterpret_cast<const v4*>(src + 4 + 4 * g);
-    }
-  };
+  auto load_state = [&](const float* src, v4& X, v4& Hs) { real_load_state(tile, g, src, X, Hs); };
   auto store_state = [&](float* dst, const v4& X, const v4& Hs) {
-    if (!live) return;
-    if constexpr (Tile::kRagged) {
-      if (g0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dst[r] = X[r];
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (4 * g + r < M) dst[4 + 4 * g + r] = Hs[r];
-    } else {
-      if (g0) *reinterpret_cast<v4*>(dst) = X;
-      *reinterpret_cast<v4*>(dst + 4 + 4 * g) = Hs;
-    }
+    if (live) real_store_state(tile, g, dst, X, Hs);
   };
-  auto set_dose = [&](Stage& s, float t) {
-    s.dv = 0.f;
-    s.ddk = 0.f;
-    if (g0) {
-      const DoseK d = real_dose(a, p, t, nn.kel);
-      s.dv = d.v;
-      s.ddk = d.dk;
-    }
-  };
+  auto set_dose = [&](Stage& s, float t) { real_set_dose(a, p, nn.kel, g0, s, t); };
 
   if constexpr (!BWD) {
     v4 X, Hs;
@@ -394,31 +495,7 @@ HODE_DEV void real_mf_body(const RealArgs& a, const Tile tile, float* lds) {
     Stage s;
     for (int n = 0; n + 1 < a.T; ++n) {
       const RStageTimes st(a.t, n, a.perturb, METHOD);
-      const float dt = st.dt;
-      v4 k1H;
-      s.X = X; s.Hs = Hs; set_dose(s, st.t_first);
-      nn.rhs(s, k1H);
-      const v4 k1X = s.KX;
-      if constexpr (METHOD == HODE_METHOD_EULER) {
-        X = X + dt * k1X; Hs = Hs + dt * k1H;
-      } else if constexpr (METHOD == HODE_METHOD_MIDPOINT) {
-        v4 k2H;
-        s.X = X + (0.5f * dt) * k1X; s.Hs = Hs + (0.5f * dt) * k1H; set_dose(s, st.ta);
-        nn.rhs(s, k2H);
-        X = X + dt * s.KX; Hs = Hs + dt * k2H;
-      } else {
-        v4 k2H, k3H, k4H;
-        s.X = X + (dt * k1X) * c13; s.Hs = Hs + (dt * k1H) * c13; set_dose(s, st.ta);
-        nn.rhs(s, k2H);
-        const v4 k2X = s.KX;
-        s.X = X + dt * (k2X - k1X * c13); s.Hs = Hs + dt * (k2H - k1H * c13); set_dose(s, st.tb);
-        nn.rhs(s, k3H);
-        const v4 k3X = s.KX;
-        s.X = X + dt * ((k1X - k2X) + k3X); s.Hs = Hs + dt * ((k1H - k2H) + k3H); set_dose(s, st.t_last);
-        nn.rhs(s, k4H);
-        X = X + ((k1X + 3.0f * (k2X + k3X)) + s.KX) * (dt * 0.125f);
-        Hs = Hs + ((k1H + 3.0f * (k2H + k3H)) + k4H) * (dt * 0.125f);
-      }
+      real_step_fwd<METHOD>(nn, s, st, X, Hs, set_dose);
       store_state(a.h + (size_t)(n + 1) * row + (size_t)p * D, X, Hs);
     }
   } else {
@@ -449,26 +526,12 @@ HODE_DEV void real_mf_body(const RealArgs& a, const Tile tile, float* lds) {
 
     for (int n = a.T - 2; n >= 0; --n) {
       const RStageTimes st(a.t, n, a.perturb, METHOD);
-      const float dt = st.dt;
       float* tp0 = a.tape + (size_t)n * NS * tstride + p;
       v4 X, Hs;
       load_state(a.h + (size_t)n * row + (size_t)p * D, X, Hs);
       Stage s[NS];
       v4 kH[NS];
-      s[0].X = X; s[0].Hs = Hs; set_dose(s[0], st.t_first);
-      nn.rhs(s[0], kH[0]);
-      if constexpr (METHOD == HODE_METHOD_MIDPOINT) {
-        s[1].X = X + (0.5f * dt) * s[0].KX; s[1].Hs = Hs + (0.5f * dt) * kH[0]; set_dose(s[1], st.ta);
-        nn.rhs(s[1], kH[1]);
-      } else if constexpr (METHOD == HODE_METHOD_RK4_38) {
-        s[1].X = X + (dt * s[0].KX) * c13; s[1].Hs = Hs + (dt * kH[0]) * c13; set_dose(s[1], st.ta);
-        nn.rhs(s[1], kH[1]);
-        s[2].X = X + dt * (s[1].KX - s[0].KX * c13); s[2].Hs = Hs + dt * (kH[1] - kH[0] * c13); set_dose(s[2], st.tb);
-        nn.rhs(s[2], kH[2]);
-        s[3].X = X + dt * ((s[0].KX - s[1].KX) + s[2].KX); s[3].Hs = Hs + dt * ((kH[0] - kH[1]) + kH[2]);
-        set_dose(s[3], st.t_last);
-        nn.rhs(s[3], kH[3]);
-      }
+      HODE_REAL_STEP_STAGES(METHOD, nn, s, kH, st, X, Hs, set_dose)
       auto vjp = [&](int q, const v4& gX, const v4& gH, v4& aX, v4& aH) {
         v4 U1[NT2], ur, uz, uh;
         float u12, u22;
@@ -493,35 +556,7 @@ HODE_DEV void real_mf_body(const RealArgs& a, const Tile tile, float* lds) {
         tape_tile(tp, tl.uz(), M, uz);
         tape_tile(tp, tl.uh(), M, uh);
       };
-      v4 aX, aH;
-      if constexpr (METHOD == HODE_METHOD_EULER) {
-        vjp(0, dt * lamX, dt * lamH, aX, aH);
-        lamX = lamX + aX; lamH = lamH + aH;
-      } else if constexpr (METHOD == HODE_METHOD_MIDPOINT) {
-        vjp(1, dt * lamX, dt * lamH, aX, aH);
-        lamX = lamX + aX; lamH = lamH + aH;
-        const v4 gX = (0.5f * dt) * aX, gH = (0.5f * dt) * aH;
-        vjp(0, gX, gH, aX, aH);
-        lamX = lamX + aX; lamH = lamH + aH;
-      } else {
-        const float w1 = dt * 0.125f, w3 = dt * 0.375f;
-        vjp(3, w1 * lamX, w1 * lamH, aX, aH);
-        v4 daX = dt * aX, daH = dt * aH;
-        v4 g1X = w1 * lamX + daX, g1H = w1 * lamH + daH;
-        v4 g2X = w3 * lamX - daX, g2H = w3 * lamH - daH;
-        const v4 gX = w3 * lamX + daX, gH = w3 * lamH + daH;
-        lamX = lamX + aX; lamH = lamH + aH;
-        vjp(2, gX, gH, aX, aH);
-        daX = dt * aX; daH = dt * aH;
-        g2X = g2X + daX; g2H = g2H + daH;
-        g1X = g1X - c13 * daX; g1H = g1H - c13 * daH;
-        lamX = lamX + aX; lamH = lamH + aH;
-        vjp(1, g2X, g2H, aX, aH);
-        g1X = g1X + c13 * (dt * aX); g1H = g1H + c13 * (dt * aH);
-        lamX = lamX + aX; lamH = lamH + aH;
-        vjp(0, g1X, g1H, aX, aH);
-        lamX = lamX + aX; lamH = lamH + aH;
-      }
+      HODE_REAL_STEP_CHAIN(METHOD, st.dt, lamX, lamH, vjp)
       v4 ghX, ghH;
       load_state(a.grad_h + (size_t)n * row + (size_t)p * D, ghX, ghH);
       lamX = lamX + lv * ghX; lamH = lamH + lv * ghH;

@@ -1,5 +1,7 @@
 """Fixed-grid solve of the real-data hybrid ODE (reference ``RocheODEReal``, ``model.py:570-657``) on the gfx950 kernels:
-libhode.so at the latent sizes 4 and 20, libhode_real_dims.so (matrix cores, on-chip weight gradients) at 5 .. 19.
+libhode.so at the latent sizes 4 and 20, libhode_real_dims.so (matrix cores, on-chip weight gradients) at 5 .. 19; the
+one-step-ahead solve (``hode.real_step``: a start state per interval) runs through the same autograd function on
+libhode_real_step.so.
 
 The backward kernel returns ``grad_y0`` and the gradients of the three scalars, and tapes the operands of every linear
 layer's weight gradient; they are contracted here with batched BLAS GEMMs and returned as one flat gradient matching
@@ -11,13 +13,14 @@ import torch
 
 from . import _lib as L
 from . import _real_dims_lib as RD
+from . import _real_step_lib as RS
 from .solver import _f32c, _require_gpu, _stream
 
 _STAGES = {L.METHOD_EULER: 1, L.METHOD_MIDPOINT: 2, L.METHOD_RK4_38: 4}
 
 
 def _desc(y0, t, act, theta, wflat, h, method, perturb, hidden):
-    B, D = y0.shape
+    B, D = y0.shape[-2:]
     d = L.new_solve_desc()
     d.rhs_kind, d.method, d.perturb = L.RHS_ROCHE_REAL, method, int(perturb)
     d.batch, d.latent_dim, d.n_times, d.hidden_dim, d.n_action_times = B, D, t.numel(), hidden, act.shape[0]
@@ -26,16 +29,22 @@ def _desc(y0, t, act, theta, wflat, h, method, perturb, hidden):
 
 
 class _RealFixedGrid(torch.autograd.Function):
-    """Gradients for y0, theta, wflat; none for t and the action table act (their .grad stays None)."""
+    """Gradients for y0, theta, wflat; none for t and the action table act (their .grad stays None).
+
+    A 3-D ``y0`` (N, B, D) with a 2-D ``t`` (N, S + 1) is the one-step-ahead solve (``lib`` is then the step library of
+    ``hode._real_step_lib``): interval i starts from ``y0[i]`` and runs over the S solver steps of ``t[i]``; ``h`` is
+    (N + 1, B, D) with the zero row first, ``grad_y0`` has ``y0``'s shape."""
 
     @staticmethod
     def forward(ctx, y0, theta, wflat, t, act, method, perturb, hidden, lanes, lib):
         _require_gpu(y0, theta, wflat, t, act)
         y0c, thc, wc, tc, ac = _f32c(y0), _f32c(theta), _f32c(wflat), _f32c(t), _f32c(act)
-        B, D = y0c.shape
+        B, D = y0c.shape[-2:]
         M = D - 4
         assert wc.numel() == 9 * hidden + 2 + 3 * M * M, "flat weight buffer has the wrong length"
-        h = torch.empty((tc.numel(), B, D), device=y0.device, dtype=torch.float32)
+        step = y0c.dim() == 3
+        assert not step or (RS.is_step_library(lib) and tc.dim() == 2 and tc.shape[0] == y0c.shape[0]), "step solve: t is (N, S + 1)"
+        h = torch.empty((y0c.shape[0] + 1 if step else tc.numel(), B, D), device=y0.device, dtype=torch.float32)
         d = _desc(y0c, tc, ac, thc, wc, h, method, perturb, hidden)
         d.lanes_per_patient = lanes
         n = lib.hode_workspace_bytes(d, L.WS_RK_FWD)  # the per-patient dose table
@@ -43,25 +52,32 @@ class _RealFixedGrid(torch.autograd.Function):
         d.workspace, d.workspace_bytes = ws.data_ptr(), n
         with torch.cuda.device(y0.device):
             L.check(lib.hode_rk_fwd(d, _stream()), "hode_rk_fwd[real]")
-        ctx.save_for_backward(h, thc, wc, tc, ac)
+        if step:  # h[0] is the zero row there: the start states are the input
+            ctx.save_for_backward(y0c, h, thc, wc, tc, ac)
+        else:
+            ctx.save_for_backward(h, thc, wc, tc, ac)
         ctx.meta = (method, int(perturb), int(hidden), lanes, lib)
         return h
 
     @staticmethod
     def backward(ctx, grad_h):
-        h, thc, wc, tc, ac = ctx.saved_tensors
         method, perturb, H, lanes, lib = ctx.meta
+        if RS.is_step_library(lib):
+            y0c, h, thc, wc, tc, ac = ctx.saved_tensors
+        else:
+            h, thc, wc, tc, ac = ctx.saved_tensors
+            y0c = h[0]
         T, B, D = h.shape
         gh = _f32c(grad_h)
-        gy0 = torch.empty((B, D), device=h.device, dtype=torch.float32)
+        gy0 = torch.empty(y0c.shape, device=h.device, dtype=torch.float32)
         gth = torch.zeros(L.N_THETA, device=h.device, dtype=torch.float32)
-        d = _desc(h[0], tc, ac, thc, wc, h, method, perturb, H)
+        d = _desc(y0c, tc, ac, thc, wc, h, method, perturb, H)
         d.lanes_per_patient = lanes
         d.grad_h, d.grad_y0, d.grad_theta = gh.data_ptr(), gy0.data_ptr(), gth.data_ptr()
         # matrix-core kernels (D = 20, hidden <= 64; the side library at every size it serves): the weight gradients are
         # accumulated on chip into this flat buffer; the lane-per-patient kernels (lanes_per_patient = 1, D = 4,
         # hidden > 64) tape the GEMM operands for contract_tape
-        onchip = RD.is_side_library(lib) or (D == 20 and H <= 64 and lanes != 1)
+        onchip = RD.is_side_library(lib) or RS.is_step_library(lib) or (D == 20 and H <= 64 and lanes != 1)
         if onchip:
             gw = torch.zeros_like(wc)
             d.grad_w1 = gw.data_ptr()

@@ -614,6 +614,22 @@ class RocheODEReal(nn.Module):
             t, step_size)
 
 
+    def hode_solve_steps(self, init, t, method, options):
+        """One-step-ahead solve (reference DecoderReal.forward with a 3-D ``init``): interval i of ``t`` integrated on its
+        own from ``init[i]``; h (len(t), B, D) with the zero row first (``hode.real_step.real_step_solve``)."""
+        if self.dosage is None:
+            raise RuntimeError("RocheODEReal: call set_action_static(a, s) before integrating")
+        from hode import real_step
+        if method == "dopri5":
+            raise hode.HodeConfigError("hode: RocheODEReal is built for the fixed-grid methods (euler, midpoint, rk4); "
+                                       "dopri5 with options['step_t'] is not supported")
+        options = dict(options)
+        theta = torch.stack([self.k_immunity, self.kel, self.kel2])
+        dose = self.dosage[..., 0] if self.dosage.shape[-1] == 1 else self.dosage.sum(-1)
+        return real_step.real_step_solve(init, theta, self.flat_weights(), t, dose, self.hidden_dim, method=method,
+                                         perturb=bool(options.pop("perturb", False)), step_size=options.pop("step_size", None))
+
+
 class _NeuralODERealBase(nn.Module):
     """Shared body of the neural ODE baselines of the real-data experiment (reference model.py:660-769): an MLP on
     [y, dose(t)] with dose(t) = cumsum(action, 0)[int(t)] (zeros once int(t) >= Ta).  ``forward`` is the reference's eager
@@ -779,7 +795,12 @@ def _tall_mlp(seq, x):
 class DecoderReal(nn.Module):
     """z0 -> h over t = t0-1 .. t_max-1 -> MLP readout, first output row dropped (model.py:772-862).  ``ode_type``
     "neural" / "2nd" build the neural ODE baselines (``NeuralODEReal`` / ``NeuralODEReal2nd``), which run on the GPU
-    kernels only: constructing them on a non-HIP device raises ``HodeConfigError``; anything else is the hybrid rhs."""
+    kernels only: constructing them on a non-HIP device raises ``HodeConfigError``; anything else is the hybrid rhs.
+
+    A 3-D ``init`` (>= t_max - 1, B, D) is the reference's one-step-ahead mode (model.py:838-861; the hybrid rhs only):
+    interval i = t[i] -> t[i + 1], i < t_max - 1, is integrated on its own from ``init[i]``; ``h`` is the end states behind a
+    zero row, (t_max, B, D), and row 0 of ``x_hat`` is zero.  With ``hode.odeint`` all intervals run in one kernel launch
+    per direction (``hode.real_step``); with any other ``_odeint`` they are the reference's loop of solver calls."""
 
     def __init__(self, obs_dim, latent_dim, action_dim, static_dim, hidden_dim, t_max, step_size, t0=0, method="dopri5",
                  ode_step_size=None, ode_type="neural", device=None, dtype=DTYPE):
@@ -811,19 +832,44 @@ class DecoderReal(nn.Module):
 
     def forward(self, init, a, s):
         self.ode.set_action_static(a, s)
-        if init.dim() != 2:
-            raise hode.HodeConfigError("DecoderReal: per-step initial states (3-D init) are outside the accelerated path")
         h = self.latent(init, a, s)
         if h.is_cuda and h.shape[0] * h.shape[1] >= 65536:
-            return _tall_mlp(self.output_function, h)[1:], h
-        return self.output_function(h)[1:], h
+            x_hat = _tall_mlp(self.output_function, h)[1:]
+        else:
+            x_hat = self.output_function(h)[1:]
+        if init.dim() != 2:  # the reference's `x_hat[0] = 0.0`, without a write into a view autograd needs
+            x_hat = torch.cat([torch.zeros_like(x_hat[:1]), x_hat[1:]], dim=0)
+        return x_hat, h
 
     def latent(self, init, a, s):
-        """Latent trajectory h (T - t0 + 1, B, D) only (row 0 = the state at t0 - 1, which the readout drops)."""
+        """Latent trajectory h (T - t0 + 1, B, D) only (row 0 = the state at t0 - 1, which the readout drops); for a 3-D
+        ``init`` the one-step-ahead states (t_max, B, D) behind their zero row."""
         self.ode.set_action_static(a, s)
         if init.dim() != 2:
-            raise hode.HodeConfigError("DecoderReal: per-step initial states (3-D init) are outside the accelerated path")
+            return self._latent_steps(init)
         return self._odeint(self.ode, init, self.t, method=self.method, options=dict(self.options), rtol=self.rtol, atol=self.atol)
+
+    def _latent_steps(self, init):
+        if not isinstance(self.ode, RocheODEReal):
+            raise hode.HodeConfigError("DecoderReal(%s): per-step initial states (3-D init) are served by the hybrid decoder "
+                                       "(ode_type='hybrid') only" % self.model_name)
+        n = int(self.t_max) - 1
+        if self.t.numel() < self.t_max:
+            raise hode.HodeConfigError("DecoderReal: per-step initial states (3-D init) need a grid of at least t_max = %d points, this "
+                                       "decoder's has %d (t0 = %s): the reference hands the solver fewer than two time points for "
+                                       "the last intervals there, and nothing defines the result" % (self.t_max, self.t.numel(), self.t0))
+        if init.dim() != 3 or init.shape[0] < n:
+            raise hode.HodeConfigError("DecoderReal: per-step initial states are (>= t_max - 1 = %d, B, D), one row per interval; "
+                                       "got %s" % (n, tuple(init.shape)))
+        if self._odeint is hode.odeint:
+            cache = getattr(self, "_step_grid", None)   # the same grid tensor at every call: its table is cached on identity
+            if cache is None or cache[0] is not self.t or cache[1] != self.t._version:
+                cache = (self.t, self.t._version, self.t[: n + 1])
+                self._step_grid = cache
+            return self.ode.hode_solve_steps(init, cache[2], self.method, self.options)
+        ends = [self._odeint(self.ode, init[i], self.t[i:i + 2], method=self.method, options=dict(self.options), rtol=self.rtol,
+                             atol=self.atol)[-1] for i in range(n)]
+        return torch.stack([torch.zeros_like(ends[0])] + ends, dim=0)
 
     def fused_likelihood_ok(self, x):
         from hode import readout
@@ -908,7 +954,8 @@ class DecoderRealBenchmark(nn.Module):
         from hode.solver import _require_gpu
         _require_gpu(init, a)
         if init.dim() != 2:
-            raise hode.HodeConfigError("DecoderRealBenchmark: per-step initial states (3-D init) are outside the accelerated path")
+            raise hode.HodeConfigError("DecoderRealBenchmark: per-step initial states (3-D init) are outside the accelerated path; "
+                                       "DecoderReal(ode_type='hybrid') serves them")
         idx, tau, max_row = self._step_tables(init.device)
         if self.ode_type == "tlstm":
             r = self.rnn
