@@ -17,7 +17,8 @@ latent ODE is integrated by the gfx950 kernels of ``libhode.so`` (``hode.odeint`
     EncoderPlanarLSTM / VariationalInferenceFlow (planar-flow posterior)   model.py:48-153, 1299-1380 (hode.flow kernels)
     LSTMBaseline (sequence-to-sequence LSTM forecaster)                    model.py:322-380  (hode.lstm.lstm_sequence)
 
-Out of scope: Sylvester flows (unused by the reference).
+The Sylvester flows of the reference's ``flow.py`` (unused by its ``model.py``) are in ``flow.Sylvester``,
+``flow.TriangularSylvester`` and ``flow.sylvester_chain`` (libhode_sylvester.so).
 """
 
 from __future__ import annotations
