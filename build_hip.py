@@ -14,7 +14,8 @@ count; SEQUENCE_LIBRARIES libhode_lstm_seq.so (C ABI include/hode_lstm_seq.h), t
 under their all-steps policy (the hidden state of every step), the LSTM units compiled a second time; STEP_LIBRARIES
 libhode_real_step.so (C ABI include/hode_real_step.h), the one-step-ahead solve of the real-data hybrid rhs (a start state
 per interval), one unit per hidden-tile count; FLOW_LIBRARIES libhode_sylvester.so (C ABI include/hode_sylvester.h), the
-chain of Sylvester flows, a single unit.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
+chain of Sylvester flows, a single unit; POSTERIOR_LIBRARIES libhode_snf.so (C ABI include/hode_snf.h), the Sylvester-flow
+posterior from the encoder's raw heads with its Monte-Carlo KL, a single unit.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
 depfile, its flags or this script changed), links each library whose objects are newer than it, and writes
 digest(<library>) next to it as <library>.so.digest; tests and hode/_loader.py compare that stamp with the tree."""
 import argparse
@@ -199,9 +200,16 @@ FLOW_LIBRARIES = {lib.name: lib for lib in (
 )}
 
 
+#: the Sylvester-flow posterior (flow.sylvester_posterior_sample, model.EncoderSylvesterLSTM), same rows; a table of its own
+#: because tests pin the names of the other tables.  `extra` lists every header of csrc/ the unit includes.
+POSTERIOR_LIBRARIES = {lib.name: lib for lib in (
+    _side("snf", PKG + "/csrc/hode_common.hpp"),
+)}
+
+
 def _library(name):
     for table in (LIBRARIES, DATA_LIBRARIES, TEST_LIBRARIES, SOLVER_LIBRARIES, ROCHE_LIBRARIES, REAL_LIBRARIES,
-                  SEQUENCE_LIBRARIES, STEP_LIBRARIES, FLOW_LIBRARIES):
+                  SEQUENCE_LIBRARIES, STEP_LIBRARIES, FLOW_LIBRARIES, POSTERIOR_LIBRARIES):
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -210,7 +218,8 @@ def _library(name):
 def all_libraries():
     return (list(LIBRARIES.values()) + list(DATA_LIBRARIES.values()) + list(TEST_LIBRARIES.values())
             + list(SOLVER_LIBRARIES.values()) + list(ROCHE_LIBRARIES.values()) + list(REAL_LIBRARIES.values())
-            + list(SEQUENCE_LIBRARIES.values()) + list(STEP_LIBRARIES.values()) + list(FLOW_LIBRARIES.values()))
+            + list(SEQUENCE_LIBRARIES.values()) + list(STEP_LIBRARIES.values()) + list(FLOW_LIBRARIES.values())
+            + list(POSTERIOR_LIBRARIES.values()))
 
 
 OUT = LIBRARIES["libhode.so"].out

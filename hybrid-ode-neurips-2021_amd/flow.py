@@ -4,7 +4,11 @@
 ``Planar`` is eager arithmetic: the training and evaluation hot path runs the whole planar stack with its Monte-Carlo KL
 in ``hode.flow`` (libhode_flow.so), and this module is the per-draw call surface and the CPU path.  The Sylvester modules
 run one fused kernel each way on HIP tensors (libhode_sylvester.so through ``hode.sylvester``, the K = 1, S = 1 case of
-``sylvester_chain``) and eager arithmetic on CPU tensors; ``sylvester_chain`` is the K-flow, S-draw call."""
+``sylvester_chain``) and eager arithmetic on CPU tensors; ``sylvester_chain`` is the K-flow, S-draw call.
+``sylvester_posterior_sample`` is the Sylvester-flow posterior (LHM-SNF) built on them: the encoder's raw heads in, the
+draws and their Monte-Carlo KL out, one fused kernel each way on HIP tensors (libhode_snf.so through ``hode.snf``)."""
+
+import math
 
 import torch
 import torch.nn as nn
@@ -117,6 +121,95 @@ def sylvester_chain(z0, r1, r2, b, q=None, perm=None, want_log_diag=False):
     log_diag = torch.stack(diags, dim=-2)
     logdet = log_diag.sum(dim=(-2, -1))
     return (z, logdet, log_diag) if want_log_diag else (z, logdet)
+
+
+# ------------------------------------------------------------------------------------ the Sylvester-flow posterior
+_LOG_SQRT_2PI = 0.9189385332046727
+_PRIOR_RATE = 100.0  # model.ExponentialPrior.rate: the prior of the kernels' KL
+
+
+class _SylvesterPosterior(torch.autograd.Function):
+    """``hode.snf``'s two launches as one differentiable call.  Gradients for every raw head; none for the noise."""
+
+    @staticmethod
+    def forward(ctx, mu, log_var, full_d, diag1, diag2, bias, v, noise, s_kl, want_z):
+        from hode.snf import snf_forward
+        ctx.set_materialize_grads(False)  # an unused output arrives as None: its gradient input stays NULL
+        z_out, kl, ws = snf_forward(mu, log_var, full_d, diag1, diag2, bias, v, noise, s_kl, want_z)
+        ctx.save_for_backward(mu, log_var, full_d, diag1, diag2, bias, v, noise, ws)
+        ctx.s_kl = s_kl
+        if z_out is None:
+            z_out = kl.new_zeros(())  # placeholder output: no gradient flows into it
+            ctx.mark_non_differentiable(z_out)
+        return z_out, kl
+
+    @staticmethod
+    def backward(ctx, g_z, g_kl):
+        if g_z is not None and g_z.dim() != 3:
+            g_z = None
+        if g_z is None and g_kl is None:
+            return (None,) * 10  # nothing to propagate: no launch
+        from hode.snf import snf_backward
+        mu, log_var, full_d, diag1, diag2, bias, v, noise, ws = ctx.saved_tensors
+        grads = snf_backward(mu, log_var, full_d, diag1, diag2, bias, v, noise, ws, ctx.s_kl, g_z, g_kl)
+        return grads + (None, None, None)
+
+
+def sylvester_flow_parameters(full_d, diag1, diag2, v=None):
+    """The flow parameters of the Sylvester posterior from the encoder's raw heads, in eager arithmetic: full_d
+    (B, K, D, D), diag1, diag2 (B, K, D), v (B, K, H, D) or None.  With U the strictly-upper mask
+
+        r1 = U * full_d   + diag(tanh(diag1))
+        r2 = U * full_d^T + diag(tanh(diag2))          (|r1_mm r2_mm| < 1: every flow is invertible)
+
+    Returns ``(r1, r2, q, perm)`` for ``sylvester_chain``.  Triangular type (v None): q None and perm (K, D) the identity
+    for even flows, the flip D-1 .. 0 for odd ones (an involution, so ``sylvester_chain``'s forward gather is the inverse
+    permutation).  Householder type: perm None and q (B, K, D, D) = (I - 2 v0 v0^T) ... (I - 2 v_{H-1} v_{H-1}^T) with
+    vh = v[:, :, h] / |v[:, :, h]|_2, orthogonal by construction."""
+    B, K, D, _ = full_d.shape
+    upper = torch.triu(torch.ones(D, D, dtype=full_d.dtype, device=full_d.device), diagonal=1)
+    r1 = upper * full_d + torch.diag_embed(torch.tanh(diag1))
+    r2 = upper * full_d.transpose(-1, -2) + torch.diag_embed(torch.tanh(diag2))
+    if v is None:
+        idx = torch.arange(D, device=full_d.device)
+        perm = torch.stack([idx if k % 2 == 0 else idx.flip(0) for k in range(K)])
+        return r1, r2, None, perm
+    vh = v / torch.linalg.vector_norm(v, dim=-1, keepdim=True)
+    q = torch.eye(D, dtype=full_d.dtype, device=full_d.device).expand(B, K, D, D)
+    for h in range(v.shape[2]):
+        w = vh[:, :, h]                                                    # (B, K, D)
+        q = q - 2.0 * torch.matmul(q, w.unsqueeze(-1)) * w.unsqueeze(-2)   # Q (I - 2 w w^T)
+    return r1, r2, q, None
+
+
+def sylvester_posterior_sample(mu, log_var, full_d, diag1, diag2, bias, v, noise, s_kl=1, want_z=True):
+    """Sylvester-flow draws and their Monte-Carlo KL against the Exponential(100) prior.
+
+    mu, log_var (B, D); full_d (B, K, D, D); diag1, diag2, bias (B, K, D): the encoder's raw heads; v (B, K, H, D) for the
+    Householder type or None for the triangular type; noise (S, B, D) standard-normal draws.
+
+        z0    = noise * exp(0.5 log_var) + mu
+        z_K   = the K flows of ``sylvester_chain`` with ``sylvester_flow_parameters(full_d, diag1, diag2, v)``
+        z_out = exp(z_K - 5);   logdet = the chain's + sum_d (z_K - 5)
+        kl_s  = sum_d log N(z0; mu, exp(0.5 log_var)) - logdet - sum_d (log 100 - 100 z_out)
+
+    Returns ``z_out`` (S, B, D) -- ``None`` when ``want_z`` is False -- and ``kl`` (B,), the mean of kl_s over the draws
+    ``s_kl .. S-1``.  HIP tensors run one fused kernel each way (libhode_snf.so; domain D 1 .. 32, K 1 .. 16, S 1 .. 256,
+    H 0 .. 8, B >= 1, 0 <= s_kl < S; outside it ``HodeConfigError``); CPU tensors run the same arithmetic eagerly."""
+    if mu.is_cuda:
+        z_out, kl = _SylvesterPosterior.apply(mu, log_var, full_d, diag1, diag2, bias, v, noise, int(s_kl), bool(want_z))
+        return (z_out if want_z else None), kl
+    if not 0 <= s_kl < noise.shape[0]:
+        raise ValueError("sylvester_posterior_sample: s_kl %r outside 0..%d" % (s_kl, noise.shape[0] - 1))
+    r1, r2, q, perm = sylvester_flow_parameters(full_d, diag1, diag2, v)
+    sigma = torch.exp(0.5 * log_var)
+    z0 = noise * sigma + mu
+    z, logdet = sylvester_chain(z0, r1, r2, bias, q, perm)
+    z_out = torch.exp(z - 5.0)
+    logdet = logdet + torch.sum(z - 5.0, dim=-1)
+    log_q = (-((z0 - mu) ** 2) / (2 * sigma ** 2) - sigma.log() - _LOG_SQRT_2PI).sum(dim=-1) - logdet
+    log_p = (math.log(_PRIOR_RATE) - _PRIOR_RATE * z_out).sum(dim=-1)
+    return (z_out if want_z else None), torch.mean((log_q - log_p)[s_kl:], dim=0)
 
 
 def _single_step(zk, r1, r2, b, q, perm, sum_ldj):

@@ -18,7 +18,9 @@ latent ODE is integrated by the gfx950 kernels of ``libhode.so`` (``hode.odeint`
     LSTMBaseline (sequence-to-sequence LSTM forecaster)                    model.py:322-380  (hode.lstm.lstm_sequence)
 
 The Sylvester flows of the reference's ``flow.py`` (unused by its ``model.py``) are in ``flow.Sylvester``,
-``flow.TriangularSylvester`` and ``flow.sylvester_chain`` (libhode_sylvester.so).
+``flow.TriangularSylvester`` and ``flow.sylvester_chain`` (libhode_sylvester.so).  ``EncoderSylvesterLSTM`` is
+the posterior they were written for (LHM-SNF; no counterpart in the reference's ``model.py``): ``VariationalInferenceFlow``
+and ``training_utils.evaluate_flow`` take it in ``EncoderPlanarLSTM``'s place (libhode_snf.so).
 """
 
 from __future__ import annotations
@@ -214,6 +216,129 @@ class EncoderPlanarLSTM(nn.Module):
             log_det_j = log_det_j + ld
         log_det_j = log_det_j + torch.sum(z - 5.0, dim=-1)
         return torch.exp(z - 5.0).reshape(S, B, D), log_det_j.reshape(S, B), z0
+
+    def posterior_sample(self, encoder_out, eps, s_kl=1):
+        """(z_out (S, B, D), kl (B,)) of the draws eps against the Exponential(100) prior: the fused kernel pair of
+        ``hode.flow`` on HIP tensors, ``flow_draws`` on CPU tensors."""
+        mu, log_var, u, w, b = encoder_out
+        if mu.is_cuda:
+            from hode.flow import planar_flow_sample
+            return planar_flow_sample(mu, log_var, u, w, b, eps, s_kl)
+        return _eager_posterior_sample(self, encoder_out, eps, s_kl)
+
+
+def _eager_posterior_sample(encoder, encoder_out, eps, s_kl):
+    """``posterior_sample`` of a flow encoder in eager arithmetic: its ``flow_draws`` and ``log_density`` against the
+    Exponential(100) prior, the mean over the draws s_kl .. of log q - log p."""
+    z_out, log_det_j, z0 = encoder.flow_draws(*encoder_out, eps)
+    log_q = encoder.log_density(encoder_out[0], encoder_out[1], z_out, log_det_j, z0)
+    return z_out, torch.mean((log_q - ExponentialPrior.log_density(z_out))[s_kl:], dim=0)
+
+
+class EncoderSylvesterLSTM(nn.Module):
+    """EncoderLSTM's window encoder with amortized Sylvester-flow parameters (LHM-SNF; van den Berg et al. 2018).  The
+    reference has the flows (``flow.py:62-219``) but no encoder that uses them; this one follows its ``EncoderPlanarLSTM``
+    (model.py:48-153) head for head.  ``flow_type`` is "triangular" (Q the identity / the flip, alternating) or
+    "householder" (Q a product of ``num_householder`` reflections, default D); the Bjorck-orthogonalised "orthogonal"
+    type is not implemented.
+
+    forward returns the raw heads ``(mu, log_var, full_d (B, K, D, D), diag1, diag2, bias (B, K, D), v (B, K, H, D) or
+    None)``; masks, tanh diagonals and the Householder product are ``flow.sylvester_flow_parameters``.  HIP tensors: the
+    window goes through the LSTM kernels and the heads are one product over the concatenated weights; the training and
+    evaluation paths draw all samples at once through the fused kernel pair of ``hode.snf``
+    (``flow.sylvester_posterior_sample``), where r1, r2 and Q never leave the chip.  ``reparameterize``, ``log_density``
+    and ``flow_draws`` are the per-draw surface of the planar encoder, with the same return shapes."""
+
+    FLOW_TYPES = ("triangular", "householder")
+
+    def __init__(self, input_dim, hidden_dim, output_dim, num_flows, flow_type="triangular", num_householder=None,
+                 normalize=True, device=None):
+        super().__init__()
+        if flow_type not in self.FLOW_TYPES:
+            raise ValueError("EncoderSylvesterLSTM: flow_type %r not in %r (the \"orthogonal\" type is not implemented)"
+                             % (flow_type, self.FLOW_TYPES))
+        self.device = get_device() if device is None else device
+        self.hidden_dim = hidden_dim
+        self.normalize = normalize
+        self.flow_type = flow_type
+        self.model_name = "TriangularSylvesterLSTMEncoder" if flow_type == "triangular" else "HouseholderSylvesterLSTMEncoder"
+        # creation order lstm -> lin -> log_var -> amor_d -> amor_diag1 -> amor_diag2 -> amor_b -> [amor_q] -> flow_k
+        self.lstm = nn.LSTM(input_dim, hidden_dim).to(self.device)
+        self.lin = nn.Linear(hidden_dim, output_dim).to(self.device)
+        self.log_var = nn.Linear(hidden_dim, output_dim).to(self.device)
+        self.q_z_nn_output_dim = hidden_dim
+        self.num_flows = num_flows
+        self.z_size = output_dim
+        self.num_householder = 0 if flow_type == "triangular" else (output_dim if num_householder is None else int(num_householder))
+        if flow_type == "householder" and self.num_householder < 1:
+            raise ValueError("EncoderSylvesterLSTM: num_householder %d must be >= 1" % self.num_householder)
+        self.log_det_j = 0.0
+        K, D = self.num_flows, self.z_size
+        self.amor_d = nn.Linear(self.q_z_nn_output_dim, K * D * D).to(self.device)
+        self.amor_diag1 = nn.Linear(self.q_z_nn_output_dim, K * D).to(self.device)
+        self.amor_diag2 = nn.Linear(self.q_z_nn_output_dim, K * D).to(self.device)
+        self.amor_b = nn.Linear(self.q_z_nn_output_dim, K * D).to(self.device)
+        if self.num_householder:
+            self.amor_q = nn.Linear(self.q_z_nn_output_dim, K * self.num_householder * D).to(self.device)
+        for k in range(K):
+            mod = flows.TriangularSylvester(D) if flow_type == "triangular" else flows.Sylvester(D)
+            self.add_module("flow_" + str(k), mod.to(self.device))
+
+    final_hidden = EncoderLSTM.final_hidden
+
+    def _heads(self):
+        heads = (self.lin, self.log_var, self.amor_d, self.amor_diag1, self.amor_diag2, self.amor_b)
+        return heads + ((self.amor_q,) if self.num_householder else ())
+
+    def forward(self, x, a, mask):
+        h = self.final_hidden(x, a, mask)
+        B, D, K, H = h.shape[0], self.z_size, self.num_flows, self.num_householder
+        heads = self._heads()
+        if h.is_cuda:   # one product over the concatenated heads; gradients reach every head through the cat
+            out = _TallLinear.apply(h, torch.cat([m.weight for m in heads]), torch.cat([m.bias for m in heads]))
+            outs = torch.split(out, [m.out_features for m in heads], dim=1)
+        else:
+            outs = tuple(m(h) for m in heads)
+        mu, log_var = outs[0], outs[1]
+        full_d = outs[2].reshape(B, K, D, D)
+        diag1, diag2, bias = (t.reshape(B, K, D) for t in outs[3:6])
+        v = outs[6].reshape(B, K, H, D) if H else None
+        if self.normalize:
+            mu = torch.exp(mu) / 10
+            log_var = log_var - 5.0
+        return mu, log_var, full_d, diag1, diag2, bias, v
+
+    def reparameterize(self, mu, log_var, full_d, diag1, diag2, bias, v=None):
+        r1, r2, q, perm = flows.sylvester_flow_parameters(full_d, diag1, diag2, v)
+        log_det_j = 0.0
+        z = [GaussianReparam.reparameterize(mu, log_var)]
+        for k in range(self.num_flows):
+            mod = getattr(self, "flow_" + str(k))
+            if q is None:
+                z_k, log_det_jacobian = mod._forward(z[k], r1[:, k], r2[:, k], bias[:, k], perm[k], sum_ldj=True)
+            else:
+                z_k, log_det_jacobian = mod(z[k], r1[:, k], r2[:, k], q[:, k], bias[:, k], sum_ldj=True)
+            z.append(z_k)
+            log_det_j += log_det_jacobian
+        z_exp = torch.exp(z_k - 5.0)
+        log_det_j += torch.sum(z_k - 5.0, dim=-1)
+        return mu, log_var, z_exp, log_det_j, z[0]
+
+    def log_density(self, mu, log_var, z_1, log_det_j, z0):
+        return GaussianReparam.log_density(mu, log_var, z0) - log_det_j
+
+    def flow_draws(self, mu, log_var, full_d, diag1, diag2, bias, v, eps):
+        """S reparameterize calls with given draws eps (S, B, D) as one ``flow.sylvester_chain`` call: returns z_out
+        (S, B, D), log_det_j (S, B), z0 (S, B, D)."""
+        r1, r2, q, perm = flows.sylvester_flow_parameters(full_d, diag1, diag2, v)
+        z0 = eps * torch.exp(0.5 * log_var) + mu
+        z, log_det_j = flows.sylvester_chain(z0, r1, r2, bias, q, perm)
+        return torch.exp(z - 5.0), log_det_j + torch.sum(z - 5.0, dim=-1), z0
+
+    def posterior_sample(self, encoder_out, eps, s_kl=1):
+        """(z_out (S, B, D), kl (B,)) of the draws eps against the Exponential(100) prior: the fused kernel pair of
+        ``hode.snf`` on HIP tensors, the same arithmetic eagerly on CPU tensors."""
+        return flows.sylvester_posterior_sample(*encoder_out, eps, s_kl)
 
 
 dose_schedule_index = hode.solver.dose_schedule_index
@@ -1098,12 +1223,14 @@ class VariationalInferenceReal(VariationalInference):
 
 
 class VariationalInferenceFlow:
-    """Negative ELBO with the planar-flow posterior (reference model.py:1299-1380): masked SSE of one flow draw's
+    """Negative ELBO with a flow posterior (reference model.py:1299-1380): masked SSE of one flow draw's
     decode + Monte-Carlo KL of ``mc_size`` further draws against the prior.  With ``mc_size == 1`` the decoder's draw
-    is reused and the KL term is ``mean(log_p - log_q)`` -- the reference's sign, kept as is.
+    is reused and the KL term is ``mean(log_p - log_q)`` -- the reference's sign, kept as is.  The encoder is an
+    ``EncoderPlanarLSTM`` (LHM-NF) or an ``EncoderSylvesterLSTM`` (LHM-SNF); it supplies the draws.
 
     HIP tensors: all 1 + mc_size draws come from one (S, B, D) ``randn`` block and go through one fused forward and one
-    fused backward launch (``hode.flow.planar_flow_sample``); the likelihood takes the fused readout + masked-SSE path.
+    fused backward launch (the encoder's ``posterior_sample``: ``hode.flow.planar_flow_sample`` or
+    ``flow.sylvester_posterior_sample``); the likelihood takes the fused readout + masked-SSE path.
     RNG stream: the reference draws (B, D) per ``reparameterize`` call (decoder draw first, then the KL draws); here the
     same draws come from one (1 + mc_size, B, D) tensor in the same order, so the numbers differ from a seeded reference
     run although the distribution is the same.  The prior must be ``ExponentialPrior.log_density`` on the device (the
@@ -1133,16 +1260,15 @@ class VariationalInferenceFlow:
 
     def flow_kl(self, encoder_out, eps, s_kl):
         """(z_out (S, B, D), kl (B,)): the flow draws of eps and the mean over draws s_kl.. of log q - log p."""
-        mu, log_var, u, w, b = encoder_out
+        mu, log_var = encoder_out[0], encoder_out[1]
         if self.prior_log_pdf is None:
             raise TypeError("'NoneType' object is not callable")  # the reference calls prior_log_pdf(z)
         if mu.is_cuda:
             if self.prior_log_pdf is not ExponentialPrior.log_density:
                 raise hode.HodeConfigError("VariationalInferenceFlow: the device path implements the Exponential(100) "
                                            "prior only (ExponentialPrior.log_density)")
-            from hode.flow import planar_flow_sample
-            return planar_flow_sample(mu, log_var, u, w, b, eps, s_kl)
-        z_out, log_det_j, z0 = self.encoder.flow_draws(mu, log_var, u, w, b, eps)
+            return self.encoder.posterior_sample(encoder_out, eps, s_kl)  # the encoder's fused kernel pair
+        z_out, log_det_j, z0 = self.encoder.flow_draws(*encoder_out, eps)
         log_q = self.encoder.log_density(mu, log_var, z_out, log_det_j, z0)
         return z_out, torch.mean((log_q - self.prior_log_pdf(z_out))[s_kl:], dim=0)
 

@@ -251,13 +251,11 @@ def evaluate_horizon(model, data_generator, batch_size, t0, mc_itr=10, real=Fals
 def evaluate_flow(model, data_generator, batch_size, t0, mc_itr=50, real=False):
     """Reference ``training_utils.evaluate_flow`` (:282-378) for ``VariationalInferenceFlow``: per test chunk one flow
     draw is the point estimate and ``mc_itr`` further draws form the ensemble; all 1 + mc_itr draws come from one fused
-    kernel call (``hode.flow``), the ensemble is decoded as one mc_itr * B batch and scored by the CRPS kernel, as
+    kernel call (the encoder's ``posterior_sample``: ``hode.flow`` or ``hode.snf``), the ensemble is decoded as one mc_itr * B batch and scored by the CRPS kernel, as
     ``evaluate`` does.  Kept literally from the reference: ``z0`` there is rebound by every ``reparameterize`` call, so
     ``rmse_z0`` compares the point draw with its own base sample z0 = eps * sigma + mu, and ``cprs_z0`` scores the
     ensemble against the LAST draw's base sample.  Prints the four ``name,value,sd`` lines; ``real=True`` raises
     ValueError as the reference does."""
-    from hode.flow import planar_flow_sample
-
     per_chunk = {"se_z0": [], "mse_x": [], "crps_z0": [], "crps_x": []}
     E = data_generator.expert_dim
     M = int(mc_itr)
@@ -267,9 +265,10 @@ def evaluate_flow(model, data_generator, batch_size, t0, mc_itr=50, real=False):
             x, a, mask = data["measurements"][:t0], data["actions"][:t0], data["masks"][:t0]
             if real:
                 raise ValueError
-            mu, log_var, u, w, b = model.encoder(x, a, mask)
+            encoder_out = model.encoder(x, a, mask)     # EncoderPlanarLSTM or EncoderSylvesterLSTM: the encoder draws
+            mu, log_var = encoder_out[0], encoder_out[1]
             eps = model.noise(1 + M, mu)
-            z_all, _ = planar_flow_sample(mu, log_var, u, w, b, eps, s_kl=1)
+            z_all, _ = model.encoder.posterior_sample(encoder_out, eps, 1)
             base = eps[:: max(M, 1)] * torch.exp(0.5 * log_var) + mu     # base samples of draw 0 and draw M
             z0_hat = z_all[0]
             x_hat, _ = model.decoder(z0_hat, data["actions"])
