@@ -15,7 +15,9 @@ under their all-steps policy (the hidden state of every step), the LSTM units co
 libhode_real_step.so (C ABI include/hode_real_step.h), the one-step-ahead solve of the real-data hybrid rhs (a start state
 per interval), one unit per hidden-tile count; FLOW_LIBRARIES libhode_sylvester.so (C ABI include/hode_sylvester.h), the
 chain of Sylvester flows, a single unit; POSTERIOR_LIBRARIES libhode_snf.so (C ABI include/hode_snf.h), the Sylvester-flow
-posterior from the encoder's raw heads with its Monte-Carlo KL, a single unit.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
+posterior from the encoder's raw heads with its Monte-Carlo KL, a single unit; ADAPTIVE_LIBRARIES libhode_dopri5_pp.so (C ABI
+include/hode_dopri5_pp.h), the dopri5 solve of the hybrid Roche rhs with per-patient step control, one unit per size of
+DP_DIMS.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
 depfile, its flags or this script changed), links each library whose objects are newer than it, and writes
 digest(<library>) next to it as <library>.so.digest; tests and hode/_loader.py compare that stamp with the tree."""
 import argparse
@@ -207,9 +209,27 @@ POSTERIOR_LIBRARIES = {lib.name: lib for lib in (
 )}
 
 
+def _dopri5_pp_units():
+    d = os.path.join(CSRC, "dopri5_pp")
+    # -Wno-unused-function: hode_rk_host.hpp is included for the partial fold; its Roche argument helpers are not called here
+    return [("hode_dopri5_pp", os.path.join(d, "hode_dopri5_pp.hip"), ["-Wno-unused-function"])] + \
+        [("hode_dopri5_pp_d%d" % n, os.path.join(d, "hode_dopri5_pp_dim.hip"), ["-DHODE_DIM=%d" % n]) for n in DP_DIMS]
+
+
+#: the dopri5 solve of the hybrid Roche rhs with per-patient step control (hode.patient_dopri5, RocheODE.step_control =
+#: "patient"), same rows; a table of its own because tests pin the names of the other tables.  `extra` lists every file of
+#: csrc/ the units include from outside `src_dir`.
+ADAPTIVE_LIBRARIES = {lib.name: lib for lib in (
+    Library("libhode_dopri5_pp.so", PKG + "/csrc/dopri5_pp", "include/hode_dopri5_pp.h",
+            tuple(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_lanes.hpp", "hode_roche.hpp", "hode_host.hpp",
+                                               "hode_rk_host.hpp", "hode_dopri5_kernels.hpp", "hode_side_error.hpp"))
+            + ("include/hode.h",), _dopri5_pp_units),
+)}
+
+
 def _library(name):
     for table in (LIBRARIES, DATA_LIBRARIES, TEST_LIBRARIES, SOLVER_LIBRARIES, ROCHE_LIBRARIES, REAL_LIBRARIES,
-                  SEQUENCE_LIBRARIES, STEP_LIBRARIES, FLOW_LIBRARIES, POSTERIOR_LIBRARIES):
+                  SEQUENCE_LIBRARIES, STEP_LIBRARIES, FLOW_LIBRARIES, POSTERIOR_LIBRARIES, ADAPTIVE_LIBRARIES):
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -219,7 +239,7 @@ def all_libraries():
     return (list(LIBRARIES.values()) + list(DATA_LIBRARIES.values()) + list(TEST_LIBRARIES.values())
             + list(SOLVER_LIBRARIES.values()) + list(ROCHE_LIBRARIES.values()) + list(REAL_LIBRARIES.values())
             + list(SEQUENCE_LIBRARIES.values()) + list(STEP_LIBRARIES.values()) + list(FLOW_LIBRARIES.values())
-            + list(POSTERIOR_LIBRARIES.values()))
+            + list(POSTERIOR_LIBRARIES.values()) + list(ADAPTIVE_LIBRARIES.values()))
 
 
 OUT = LIBRARIES["libhode.so"].out

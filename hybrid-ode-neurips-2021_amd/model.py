@@ -347,6 +347,61 @@ dose_schedule_index = hode.solver.dose_schedule_index
 _THETA_FIELDS = sim_config.RochConfig._fields  # == parameter creation order of the reference (model.py:468-482)
 
 
+STEP_CONTROLS = ("batch", "patient")
+
+
+def _step_control(module, options):
+    """The dopri5 step control of this call: ``options["step_control"]`` if given, else the module's ``step_control``
+    attribute, else "batch" (torchdiffeq's: one error norm and one dt for the whole batch).  "patient" gives every patient a
+    controller of its own (``hode.patient_dopri5``); anything else is refused."""
+    control = options.pop("step_control", getattr(module, "step_control", "batch"))
+    if control not in STEP_CONTROLS:
+        raise hode.HodeConfigError("hode: step_control %r is not one of %s" % (control, ", ".join(map(repr, STEP_CONTROLS))))
+    return control
+
+
+def _refuse_patient_step_control(module, options):
+    """For the rhs families without per-patient kernels: names what serves ``step_control = "patient"``."""
+    if _step_control(module, options) == "patient":
+        from hode import _dopri5_pp_lib as PL
+        raise hode.HodeConfigError("hode: %s has no per-patient step control; step_control='patient' serves %s with "
+                                   "method='dopri5'" % (type(module).__name__, PL.sizes_text()))
+
+
+class _RochePatientDopri5(torch.autograd.Function):
+    """h = odeint(RocheODE, y0, t, method="dopri5") with per-patient step control: the two launches of
+    ``hode.patient_dopri5``.  Gradients for y0, theta, w, b; none for t, dosage, dose_times (their .grad stays None).  Every
+    step size is a constant in the backward, dt_0 included."""
+
+    @staticmethod
+    def forward(ctx, y0, theta, w, b, t, dosage, dose_times, rtol, atol, ablate, grad_enabled=True):
+        from hode import patient_dopri5 as PP
+        f32c = hode.solver._f32c
+        y0c, thc, tc, dosc, dtc = f32c(y0), f32c(theta), f32c(t), f32c(dosage), f32c(dose_times)
+        wc = f32c(w) if w is not None else None
+        bc = f32c(b) if b is not None else None
+        # `needs_input_grad` reflects requires_grad, not the grad mode, and inside forward() grad mode is always off: the
+        # caller samples it before .apply() (as hode.adaptive.roche_dopri5 does).  Nothing to differentiate: no tape at all.
+        no_tape = not (grad_enabled and any(ctx.needs_input_grad[:4]))
+        h, ws, stats = PP.patient_dopri5_forward(y0c, thc, wc, bc, tc, dosc, dtc, rtol=rtol, atol=atol, ablate=ablate,
+                                                 no_tape=no_tape)
+        ctx.save_for_backward(h, thc, wc if wc is not None else thc, bc if bc is not None else thc, tc, dosc, dtc, y0c, ws,
+                              stats["n_accepted"])
+        ctx.meta = (float(rtol), float(atol), bool(ablate), w is not None, int(stats["max_steps"]))
+        return h
+
+    @staticmethod
+    def backward(ctx, grad_h):
+        from hode import patient_dopri5 as PP
+        h, thc, wc, bc, tc, dosc, dtc, y0c, ws, n_accepted = ctx.saved_tensors
+        rtol, atol, ablate, has_w, steps = ctx.meta
+        need_th = bool(ctx.needs_input_grad[1])
+        gy0, gth, gw, gb = PP.patient_dopri5_backward(y0c, thc, wc if has_w else None, bc if has_w else None, tc, dosc, dtc, h, ws,
+                                                      n_accepted, steps, hode.solver._f32c(grad_h), rtol=rtol, atol=atol,
+                                                      ablate=ablate, need_theta=need_th)
+        return gy0, gth, gw, gb, None, None, None, None, None, None, None
+
+
 class RocheODE(nn.Module):
     """Expert PK/PD block + ``tanh(W y + b)`` learned block; ``forward(t, y)`` is the rhs (model.py:446-555)."""
 
@@ -377,6 +432,9 @@ class RocheODE(nn.Module):
         # tuning knobs of the kernel dispatch (not part of the reference surface)
         self.lanes_per_patient = 0
         self.check_finite = False
+        # dopri5 only: "batch" = torchdiffeq's controller (one error norm, one dt for the whole batch); "patient" = a
+        # controller per patient (hode.patient_dopri5); options["step_control"] of hode.odeint overrides it for one call
+        self.step_control = "batch"
 
     # -- dose schedule -------------------------------------------------------------------------------------
     def set_action(self, action):
@@ -435,6 +493,13 @@ class RocheODE(nn.Module):
             raise RuntimeError("RocheODE: call set_action(a) before integrating")
         w = self.ml_net[0].weight if self.expanded else None
         b = self.ml_net[0].bias if self.expanded else None
+        control = _step_control(self, options)  # the fixed-grid methods ignore it
+        if method == "dopri5" and control == "patient":
+            from hode import patient_dopri5
+            patient_dopri5.check_domain(self.latent_dim)  # names the sizes held; nothing is loaded or launched before
+            return _RochePatientDopri5.apply(y0, self.theta_vector(), w, b, t, self.dosage,
+                                             self.times.reshape(y0.shape[0], -1).to(torch.float32), rtol, atol, bool(self.ablate),
+                                             torch.is_grad_enabled())
         from hode import _roche_dims_lib as RL
         held = RL.DIMS + (RL.LIBHODE_DP_DIMS if method == "dopri5" else RL.LIBHODE_RK_DIMS)
         if self.latent_dim not in held:
@@ -485,6 +550,7 @@ class NeuralODE(nn.Module):
     def hode_solve(self, y0, t, rtol, atol, method, options):
         if self.times is None:
             raise RuntimeError("NeuralODE: call set_action(a) before integrating")
+        _refuse_patient_step_control(self, options)
         from hode import neural
         if method == "dopri5":
             from hode import adaptive
@@ -711,6 +777,7 @@ class RocheODEReal(nn.Module):
     def hode_solve(self, y0, t, rtol, atol, method, options):
         if self.dosage is None:
             raise RuntimeError("RocheODEReal: call set_action_static(a, s) before integrating")
+        _refuse_patient_step_control(self, options)
         from hode import real
         if method == "dopri5":
             # DecoderReal hands dopri5 a `step_t` grid (model.py:826: steps are cut at the hourly dose switches); that
@@ -798,6 +865,7 @@ class _NeuralODERealBase(nn.Module):
 
     def hode_solve(self, y0, t, rtol, atol, method, options):
         from hode import neural_real, substep
+        _refuse_patient_step_control(self, options)
         neural_real.check_config(self.kind, self.latent_dim, self.hidden_dim, self.action_dim, method)
         if self.action is None:
             raise RuntimeError("%s: call set_action_static(a, s) before integrating" % type(self).__name__)

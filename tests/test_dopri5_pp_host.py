@@ -1,0 +1,362 @@
+"""CPU checks of the per-patient dopri5 path (no GPU): libhode_dopri5_pp.so's C ABI, build-table row, digest and loader
+messages, the compiled kernels against the GPU case table (tests/dopri5_pp_cases.py), the library's own refusals, the
+refusals that happen before anything is loaded, and the dispatch from hode.odeint / model.RocheODE.step_control."""
+import ctypes
+import glob
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+import torch
+
+import abi_checks
+import build_hip
+import dopri5_pp_cases as cases
+import kernel_variants as kv
+import model
+
+ROOT = build_hip.ROOT
+LIB = "libhode_dopri5_pp.so"
+FUNCTIONS = {"hode_dopri5_pp_" + n for n in ("version", "last_error_string", "workspace_bytes", "fwd", "bwd", "tape_offsets")}
+E_NULL, E_SIZE, E_UNSUPPORTED, E_WORKSPACE, E_ALIGN = -1, -2, -3, -4, -5
+CPU = torch.device("cpu")
+
+
+# ------------------------------------------------------------------------------------------------------ 1. ABI, build
+@pytest.fixture(scope="module")
+def lib():
+    from hode import _dopri5_pp_lib as PL
+    return abi_checks.built(PL.LIBRARY)
+
+
+def test_header_functions_are_exported_and_bound(lib):
+    from hode import _dopri5_pp_lib as PL
+    declared = abi_checks.declared_functions("hode_dopri5_pp.h", "hode_dopri5_pp_")
+    assert declared == {name for name, _, _ in PL.EXPORTS} == FUNCTIONS
+    for name in declared:
+        assert getattr(lib, name) is not None
+    src = abi_checks.header_text("hode_dopri5_pp.h")
+    assert "#define HODE_DOPRI5_PP_ABI_VERSION %d\n" % PL.HODE_DOPRI5_PP_ABI_VERSION in src
+    assert lib.hode_dopri5_pp_version() == PL.HODE_DOPRI5_PP_ABI_VERSION
+    assert PL.DIMS == build_hip.DP_DIMS == cases.DIMS
+    assert all(str(d) in PL.sizes_text() for d in PL.DIMS) and LIB in PL.sizes_text()
+
+
+def test_struct_layout_matches_the_c_header(tmp_path):
+    from hode import _dopri5_pp_lib as PL
+    abi_checks.assert_c_layout("hode_dopri5_pp.h", "hode_dopri5_pp_desc", PL.PpDesc, tmp_path)
+    assert PL.new_desc().struct_size == ctypes.sizeof(PL.PpDesc)
+
+
+def test_the_build_table_holds_exactly_this_library():
+    assert sorted(build_hip.ADAPTIVE_LIBRARIES) == [LIB]
+    row = build_hip.ADAPTIVE_LIBRARIES[LIB]
+    assert row in build_hip.all_libraries() and build_hip._library(LIB) is row
+    assert row.header == "include/hode_dopri5_pp.h"
+    assert row.src_dir == build_hip.PKG + "/csrc/dopri5_pp" and row.obj == os.path.join(ROOT, row.src_dir, "build")
+    units = [(n, os.path.relpath(s, ROOT).replace(os.sep, "/"), e) for n, s, e in row.units()]
+    assert units[0] == ("hode_dopri5_pp", row.src_dir + "/hode_dopri5_pp.hip", ["-Wno-unused-function"])
+    # one compile unit per latent size
+    assert units[1:] == [("hode_dopri5_pp_d%d" % d, row.src_dir + "/hode_dopri5_pp_dim.hip", ["-DHODE_DIM=%d" % d]) for d in build_hip.DP_DIMS]
+    assert row.out == os.path.join(ROOT, build_hip.PKG, "hode", LIB)
+    assert LIB not in build_hip.LIBRARIES and len(build_hip.LIBRARIES) == 4
+    assert len({lib.name for lib in build_hip.all_libraries()}) == len(build_hip.all_libraries())
+
+
+def test_library_digest_matches_sources(lib):
+    out = build_hip.ADAPTIVE_LIBRARIES[LIB].out
+    assert os.path.exists(out + ".digest"), "%s has no source digest: rebuild with `python build_hip.py`" % LIB
+    assert open(out + ".digest").read().strip() == build_hip.digest(LIB), "%s is stale: run `python build_hip.py`" % LIB
+
+
+def _includes(path, seen):
+    for inc in re.findall(r'^\s*#include\s+"([^"]+)"', open(path).read(), flags=re.M):
+        f = os.path.normpath(os.path.join(os.path.dirname(path), inc))
+        if f not in seen and os.path.exists(f):
+            seen.add(f)
+            _includes(f, seen)
+    return seen
+
+
+def test_extra_lists_every_file_the_units_include():
+    row = build_hip.ADAPTIVE_LIBRARIES[LIB]
+    hashed = set(build_hip.digest_files(LIB))
+    included = set()
+    for _, src, _ in row.units():
+        included |= {os.path.relpath(f, ROOT).replace(os.sep, "/") for f in _includes(src, {src})}
+    assert included <= hashed, sorted(included - hashed)
+    assert set(row.extra) <= included, sorted(set(row.extra) - included)
+
+
+def test_the_device_code_is_compiled_not_copied():
+    """The rhs, its VJP, the stages, the step factor, the tableau and the partial rows are the existing headers' own."""
+    src = open(os.path.join(build_hip.CSRC, "dopri5_pp", "hode_dopri5_pp_kernels.hpp")).read()
+    for name in ("roche_rhs<", "roche_vjp<", "GradAcc<", "MlSlice<", "DoseSched<", "load_theta(", "dp_stages<", "dp_step_factor(",
+                 "dp_store_grad_partials<", "dp_load_dose<", "kDpErr[", "kDpMid[", "kDpBeta[", "LaneMap<1>"):
+        assert name in src, name
+    for definition in ("HODE_DEV void roche_rhs", "HODE_DEV void roche_vjp", "HODE_DEV void dp_stages", "HODE_DEV double dp_step_factor",
+                       "constexpr float kDp", "struct GradAcc", "HODE_DEV void dp_store_grad_partials", "fold_partials_kernel"):
+        assert definition not in src, definition
+    host = open(os.path.join(build_hip.CSRC, "dopri5_pp", "hode_dopri5_pp.hip")).read()
+    assert "launch_fold_partials(" in host and "hode_side_error.hpp" in host and "__global__" not in host
+
+
+def test_a_missing_and_a_stale_library_are_refused_with_a_message(lib, tmp_path, monkeypatch):
+    from hode import HodeConfigError, _dopri5_pp_lib as PL
+    import shutil
+    library, out = PL.LIBRARY, build_hip.ADAPTIVE_LIBRARIES[LIB].out
+    assert library.check_digest and library.file_name == LIB and library.env == "HODE_DOPRI5_PP_LIBRARY"
+    monkeypatch.setattr(library, "handle", None)
+    monkeypatch.setattr(library, "directory", str(tmp_path))
+    with pytest.raises(HodeConfigError, match=r"libhode_dopri5_pp\.so not found -- build it with `python build_hip\.py`.*no CPU fallback for the dopri5 solve with per-patient step control"):
+        library.load()
+    shutil.copy(out, tmp_path / LIB)
+    (tmp_path / (LIB + ".digest")).write_text("0" * 64 + "\n")
+    with pytest.raises(HodeConfigError, match=r"libhode_dopri5_pp\.so is stale .*rebuild with `python build_hip\.py`"):
+        library.load()
+    shutil.copy(out + ".digest", tmp_path / (LIB + ".digest"))
+    assert library.load().hode_dopri5_pp_version() == library.abi_version
+
+
+def test_importing_the_package_does_not_load_the_library():
+    code = ("import sys; sys.path[:0] = %r; import hode, model; from hode import patient_dopri5, _dopri5_pp_lib as PL; "
+            "assert PL.LIBRARY.handle is None; print('ok')" % [ROOT, os.path.join(ROOT, build_hip.PKG)])
+    assert subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True).stdout.strip() == "ok"
+
+
+# ---------------------------------------------------------------------------------- 2. compiled kernels / case table
+def _objects():
+    objs = sorted(glob.glob(os.path.join(build_hip.ADAPTIVE_LIBRARIES[LIB].obj, "*.o")))
+    if not objs:
+        pytest.skip("object files are not in the tree (library shipped pre-built)")
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from kernel_descriptor import kernel_descriptors
+    return [(dem, kd) for o in objs for dem, kd in kernel_descriptors(o)]
+
+
+def test_every_compiled_kernel_is_reached_by_a_gpu_case():
+    compiled = {kv.kernel_name(dem) for dem, _ in _objects()}
+    want = cases.all_kernels() | {"hode::fold_partials_kernel"}
+    assert compiled == want, (sorted(compiled - want), sorted(want - compiled))
+    assert set().union(*(cases.kernels(c) for c in cases.CASES)) == cases.all_kernels()
+    assert len(cases.all_kernels()) == 24
+
+
+def test_the_case_table_holds_what_the_issue_lists():
+    cs = cases.CASES
+    assert {c["D"] for c in cs} == set(cases.DIMS) and {c["B"] for c in cs} == {1, 3, 21, 70}
+    assert {c["K"] for c in cs} == {1, 2} and {c["ablate"] for c in cs} == {False, True}
+    ts = {c["T"] for c in cs}
+    assert 1 in ts and 2 in ts and 20 in ts and max(ts) == 20
+    assert any(c["D"] == 12 and c["B"] == 70 and c["T"] == 20 for c in cs)
+    # every rhs body -- (Hill exponents == 2, one dose), (== 2, dose list), general -- at more than one size, both ways
+    assert {cases.bodies(c) for c in cs} == {(True, True), (True, False), (False, False)}
+    assert len({c["D"] for c in cs if cases.bodies(c) == (False, False)}) >= 3
+    assert len(set(map(cases.case_id, cs))) == len(cs) < 30
+    assert all(len(cases.subset(c["B"])) <= 5 for c in cs) and cases.subset(70) == [0, 23, 63, 64, 69] and cases.subset(3) == [0, 1, 2]
+
+
+def test_case_inputs_have_the_doses_they_name():
+    from oracle.rhs import dose_schedule
+    for c in cases.CASES:
+        inp, f = cases.setup(c)
+        dosage, times = dose_schedule(inp["actions"], f.step_size)
+        assert inp["z0"].shape == (c["B"], c["D"]) and inp["t"].numel() == c["T"] and times.shape == (c["B"], c["K"]), cases.case_id(c)
+        assert f.ablate == c["ablate"] and (float(f.HillCure) == 2.0) == (c["hill"] == "two")
+
+
+# ------------------------------------------------------------------------------------------ 3. the library's refusals
+def _desc(lib, **kw):
+    from hode import _dopri5_pp_lib as PL
+    d = PL.new_desc()
+    d.batch, d.latent_dim, d.n_times, d.n_dose, d.max_steps, d.rtol, d.atol = 5, 8, 6, 1, 40, 1e-7, 1e-8
+    for k in ("t", "y0", "dosage", "dose_times", "theta", "w1", "b1", "h", "status", "n_accepted", "n_rejected", "patient_status"):
+        setattr(d, k, 4096)  # never dereferenced: every call below is refused before a launch
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+def _refused(lib, d, code, text, bwd=False):
+    fn = lib.hode_dopri5_pp_bwd if bwd else lib.hode_dopri5_pp_fwd
+    assert fn(ctypes.byref(d), None) == code
+    assert text in lib.hode_dopri5_pp_last_error_string().decode(), lib.hode_dopri5_pp_last_error_string()
+
+
+def test_the_library_refuses_what_it_does_not_hold(lib):
+    for D in (5, 7, 10, 16, 20, 3):
+        d = _desc(lib, latent_dim=D)
+        _refused(lib, d, E_UNSUPPORTED, "latent_dim %d has no compiled kernel (have latent_dim 4, 6, 8, 12" % D)
+        assert lib.hode_dopri5_pp_workspace_bytes(ctypes.byref(d)) == 0
+    for kind in (2, 3, 4, 5):
+        _refused(lib, _desc(lib, rhs_kind=kind), E_UNSUPPORTED, "rhs_kind %d is not served here" % kind)
+    _refused(lib, _desc(lib, struct_size=8), E_SIZE, "ABI mismatch")
+    for field in ("batch", "n_times", "n_dose", "max_steps"):
+        _refused(lib, _desc(lib, **{field: 0}), E_SIZE, "bad sizes")
+    _refused(lib, _desc(lib, max_attempts=-1), E_SIZE, "bad sizes")
+    _refused(lib, _desc(lib, flags=8), E_UNSUPPORTED, "flags 8")
+    _refused(lib, _desc(lib, rtol=0.0), E_SIZE, "rtol must be > 0")
+    _refused(lib, _desc(lib, h=0), E_NULL, "must be non-NULL")
+    _refused(lib, _desc(lib, w1=0), E_NULL, "w1 / b1 required")
+    _refused(lib, _desc(lib, patient_status=0), E_NULL, "patient_status")
+    _refused(lib, _desc(lib, y0=4100), E_ALIGN, "16-byte aligned")
+    _refused(lib, _desc(lib), E_WORKSPACE, "workspace 0 B < required")
+    _refused(lib, _desc(lib), E_NULL, "grad_h / grad_y0 required", bwd=True)
+    d = _desc(lib, flags=16, grad_h=4096, grad_y0=4096, grad_w1=4096, grad_b1=4096)
+    _refused(lib, d, E_UNSUPPORTED, "no tape to sweep", bwd=True)
+    assert lib.hode_dopri5_pp_fwd(None, None) == E_NULL
+
+
+def test_workspace_layout(lib):
+    """The tape is [max_steps][B] per array behind the per-wave partial rows; without a tape the partials alone, whatever
+    the step bound."""
+    d = _desc(lib, batch=70, latent_dim=12, max_steps=100)
+    off = (ctypes.c_size_t * 5)()
+    assert lib.hode_dopri5_pp_tape_offsets(ctypes.byref(d), off) == 0
+    cells = 100 * 70
+    partials = 2 * (8 * 12 + 8 + 15) * 4
+    assert off[0] == 0 and off[1] >= partials and off[2] - off[1] >= 8 * cells and off[3] - off[2] >= 8 * cells
+    assert off[4] - off[3] >= 8 * cells and all(o % 256 == 0 for o in off)
+    total = lib.hode_dopri5_pp_workspace_bytes(ctypes.byref(d))
+    assert off[4] + cells * 12 * 4 <= total < off[4] + cells * 12 * 4 + 256
+    d.flags = 16
+    small = lib.hode_dopri5_pp_workspace_bytes(ctypes.byref(d))
+    d.max_steps = 1 << 20
+    assert lib.hode_dopri5_pp_workspace_bytes(ctypes.byref(d)) == small < 2048
+
+
+# ------------------------------------------------------------------------- 4. refusals before anything is loaded
+@pytest.fixture
+def no_library(monkeypatch):
+    from hode import _dopri5_pp_lib as PL
+
+    def boom():
+        raise AssertionError("the library was loaded")
+    monkeypatch.setattr(PL.LIBRARY, "load", boom)
+    monkeypatch.setattr(PL, "lib", boom)
+
+
+def _ode(D=6, cls=model.RocheODE, **kw):
+    torch.manual_seed(0)
+    ode = cls(D, 1, 1.0, 0.1, device=CPU, **kw)
+    a = torch.zeros(11, 3, 1)
+    a[2, :, 0] = 1.0
+    ode.set_action(a)
+    return ode, torch.rand(3, D) * 0.01, torch.arange(11, dtype=torch.float32) * 0.1
+
+
+def test_unsupported_sizes_are_refused_naming_the_sizes_held(no_library):
+    import hode
+    from hode import patient_dopri5
+    for D in (5, 7, 16, 20):
+        ode, y0, t = _ode(D)
+        ode.step_control = "patient"
+        with pytest.raises(hode.HodeConfigError, match=r"latent dimensions 4, 6, 8, 12 \(libhode_dopri5_pp\.so\) \(got latent dimension %d\)" % D):
+            hode.odeint(ode, y0, t, method="dopri5")
+    with pytest.raises(hode.HodeConfigError, match="4, 6, 8, 12"):
+        patient_dopri5.check_domain(5)
+    with pytest.raises(hode.HodeConfigError, match="at least one dose"):
+        patient_dopri5.check_domain(8, 0)
+    patient_dopri5.check_domain(12, 3)
+
+
+def test_cpu_tensors_are_refused(no_library):
+    import hode
+    ode, y0, t = _ode(6)
+    with pytest.raises(hode.HodeConfigError, match="HIP device"):
+        hode.odeint(ode, y0, t, method="dopri5", options={"step_control": "patient"})
+    ode.step_control = "patient"
+    with pytest.raises(hode.HodeConfigError, match="HIP device"):
+        hode.odeint(ode, y0, t, method="dopri5")
+
+
+def test_a_bad_step_control_is_refused(no_library):
+    import hode
+    ode, y0, t = _ode(6)
+    for bad in ("Patient", "per-patient", "", None, 1):
+        with pytest.raises(hode.HodeConfigError, match="step_control .* is not one of 'batch', 'patient'"):
+            hode.odeint(ode, y0, t, method="dopri5", options={"step_control": bad})
+        ode.step_control = bad
+        with pytest.raises(hode.HodeConfigError, match="is not one of"):
+            hode.odeint(ode, y0, t, method="rk4")
+        ode.step_control = "batch"
+    assert model.STEP_CONTROLS == ("batch", "patient") and model.RocheODE(4, 1, 1.0, 0.1, device=CPU).step_control == "batch"
+
+
+def test_the_other_rhs_families_name_what_serves_it(no_library):
+    import hode
+    ode, y0, t = _ode(6, cls=model.NeuralODE)
+    for method in ("dopri5", "rk4"):
+        with pytest.raises(hode.HodeConfigError, match=r"NeuralODE has no per-patient step control.*RocheODE.*4, 6, 8, 12"):
+            hode.odeint(ode, y0, t, method=method, options={"step_control": "patient"})
+    ode.step_control = "patient"
+    with pytest.raises(hode.HodeConfigError, match="NeuralODE has no per-patient step control"):
+        hode.odeint(ode, y0, t, method="dopri5")
+    real = model.RocheODEReal(6, 1, 1, 8, 4.0, 1.0, device=CPU)
+    real.set_action_static(torch.zeros(4, 3, 1), None)
+    with pytest.raises(hode.HodeConfigError, match="RocheODEReal has no per-patient step control"):
+        real.hode_solve(torch.zeros(3, 6), torch.arange(3.0), 1e-7, 1e-8, "midpoint", {"step_control": "patient"})
+
+
+# ----------------------------------------------------------------------------------------------------- 5. dispatch
+def test_step_control_patient_reaches_the_launch_function_and_the_default_does_not(monkeypatch):
+    import hode
+    from hode import adaptive, patient_dopri5
+    calls = {"patient": [], "batch": 0}
+
+    def fake_forward(y0, theta, w, b, t, dosage, dose_times, **kw):
+        calls["patient"].append(kw)
+        B, D = y0.shape
+        return torch.zeros(t.numel(), B, D), torch.zeros(4, dtype=torch.int32), {"n_accepted": torch.zeros(B, dtype=torch.int32), "max_steps": 7}
+
+    def fake_batch(y0, *a, **kw):
+        calls["batch"] += 1
+        return torch.zeros(11, *y0.shape)
+    monkeypatch.setattr(patient_dopri5, "patient_dopri5_forward", fake_forward)
+    monkeypatch.setattr(adaptive, "roche_dopri5", fake_batch)
+    ode, y0, t = _ode(6)
+    hode.odeint(ode, y0, t, method="dopri5")
+    hode.odeint(ode, y0, t, method="dopri5", options={"step_control": "batch"})
+    assert calls["batch"] == 2 and not calls["patient"]
+    h = hode.odeint(ode, y0, t, rtol=1e-7, atol=1e-8, method="dopri5", options={"step_control": "patient"})
+    assert h.shape == (11, 3, 6) and calls["batch"] == 2 and len(calls["patient"]) == 1
+    kw = calls["patient"][0]
+    assert kw["rtol"] == 1e-7 and kw["atol"] == 1e-8 and kw["ablate"] is False and kw["no_tape"] is False  # parameters need gradients
+    ode.step_control = "patient"
+    with torch.no_grad():
+        hode.odeint(ode, y0, t)  # dopri5 is odeint's default method
+    assert len(calls["patient"]) == 2 and calls["patient"][1]["no_tape"] is True  # grad mode sampled by the caller
+    hode.odeint(ode, y0, t, options={"step_control": "batch"})  # the option overrides the attribute for that call
+    assert calls["batch"] == 3 and len(calls["patient"]) == 2
+    # the decoder reaches it through hode_solve: decoder.ode.step_control = "patient" is all a user sets
+    torch.manual_seed(1)
+    dec = model.RocheExpertDecoder(5, 6, 1, 1.0, 0.1, method="dopri5", device=CPU)
+    a = torch.zeros(11, 3, 1)
+    a[4, :, 0] = 2.0
+    dec.latent(torch.rand(3, 6) * 0.01, a)
+    assert calls["batch"] == 4
+    dec.ode.step_control = "patient"
+    dec.latent(torch.rand(3, 6) * 0.01, a)
+    assert len(calls["patient"]) == 3 and calls["batch"] == 4
+
+
+def test_the_fixed_grid_methods_ignore_it(monkeypatch):
+    import hode
+    seen = []
+    monkeypatch.setattr(hode, "roche_solve", lambda *a, **kw: seen.append(kw["method"]) or torch.zeros(11, 3, 6))
+    ode, y0, t = _ode(6)
+    ode.step_control = "patient"
+    hode.odeint(ode, y0, t, method="rk4")
+    hode.odeint(ode, y0, t, method="euler", options={"step_control": "patient"})
+    assert seen == ["rk4", "euler"]
+
+
+def test_the_autograd_function_lives_next_to_the_module_it_serves():
+    """tests/test_binding_case_coverage.py walks hode/*.py: only launch functions there, the Function in model.py."""
+    import test_binding_case_coverage as cov
+    found = cov.bindings()
+    assert not [b for b in found if b.startswith(("patient_dopri5.", "_dopri5_pp_lib."))], found
+    assert issubclass(model._RochePatientDopri5, torch.autograd.Function)
+    assert not cov.pointer_problems()
