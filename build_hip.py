@@ -1,29 +1,17 @@
 #!/usr/bin/env python
 """Build the gfx950 kernel libraries in-tree with hipcc: `python build_hip.py [-j N] [--force]`.
 
-LIBRARIES is the table of what is built: libhode.so (C ABI include/hode.h) and the single-unit side libraries
-libhode_flow.so, libhode_mix.so and libhode_blend.so, each with a C ABI header of its own so that its kernels stay out of
-libhode.so; DATA_LIBRARIES holds libhode_datagen.so in the same rows, and TEST_LIBRARIES libhode_probe.so (C ABI
-include/hode_probe.h), which runs the shared device helpers on their own for tests/test_hip_helpers.py and which nothing
-under hode/ loads; SOLVER_LIBRARIES libhode_neural_odd.so (C ABI include/hode_neural_odd.h), the NeuralODE kernels of
-libhode.so instantiated at the odd latent dimensions 5 .. 15, one unit per dimension; ROCHE_LIBRARIES libhode_roche_dims.so
-(C ABI include/hode_roche_dims.h), the hybrid Roche kernels at ROCHE_DIMS, the sizes 5 .. 16 libhode.so does not hold, one
-fixed-grid and one dopri5 unit per size; REAL_LIBRARIES libhode_real_dims.so (C ABI include/hode_real_dims.h), the real-data
-hybrid rhs on the matrix cores at the latent sizes 5 .. 20 with the size as a runtime argument, one unit per hidden-tile
-count; SEQUENCE_LIBRARIES libhode_lstm_seq.so (C ABI include/hode_lstm_seq.h), the LSTM window kernels of libhode.so
-under their all-steps policy (the hidden state of every step), the LSTM units compiled a second time; STEP_LIBRARIES
-libhode_real_step.so (C ABI include/hode_real_step.h), the one-step-ahead solve of the real-data hybrid rhs (a start state
-per interval), one unit per hidden-tile count; FLOW_LIBRARIES libhode_sylvester.so (C ABI include/hode_sylvester.h), the
-chain of Sylvester flows, a single unit; POSTERIOR_LIBRARIES libhode_snf.so (C ABI include/hode_snf.h), the Sylvester-flow
-posterior from the encoder's raw heads with its Monte-Carlo KL, a single unit; ADAPTIVE_LIBRARIES libhode_dopri5_pp.so (C ABI
-include/hode_dopri5_pp.h), the dopri5 solve of the hybrid Roche rhs with per-patient step control, one unit per size of
-DP_DIMS.  build() compiles the units of all of them in one thread pool (a unit is recompiled when a file of its
-depfile, its flags or this script changed), links each library whose objects are newer than it, and writes
-digest(<library>) next to it as <library>.so.digest; tests and hode/_loader.py compare that stamp with the tree."""
+LIBRARIES has one row per library: its file name in hode/, the directory of its sources, its C ABI header and its compile
+units.  build() compiles the units of all rows in one thread pool (a unit is recompiled when a file of its depfile, its flags
+or this script changed), links each library whose objects are newer than it, and writes digest(<library>) next to it as
+<library>.so.digest; tests and hode/_loader.py compare that stamp with the tree.  The digest covers the header, every source
+of the row's directory, the units' sources and everything they include from inside the tree, the flags and the units."""
 import argparse
 import concurrent.futures as cf
 import hashlib
 import os
+import posixpath
+import re
 import subprocess
 import sys
 import time
@@ -62,64 +50,10 @@ def units():
     return u
 
 
-class Library:
-    """One row of LIBRARIES: the file name of the library in hode/ and what it is built from.  `src_dir`, `header` and
-    `extra` are relative to the repository root and use "/", so that digest() is the same wherever the tree lives.
-    `extra` names what the units include from outside `src_dir` and the ABI header; `units` is a callable returning
-    [(unit name, absolute source path, extra flags)]; objects go to <src_dir>/build."""
-
-    def __init__(self, name, src_dir, header, extra, units):
-        self.name, self.src_dir, self.header, self.extra, self.units = name, src_dir, header, tuple(extra), units
-        self.out = os.path.join(ROOT, PKG, "hode", name)
-        self.obj = os.path.join(ROOT, src_dir, "build")
-
-
-def _side(name, *extra):
-    """A side library: csrc/<name>/hode_<name>.hip alone, with the shared host error helper."""
-    d = PKG + "/csrc/" + name
-    unit = ("hode_" + name, os.path.join(ROOT, d, "hode_%s.hip" % name), [])
-    return Library("libhode_%s.so" % name, d, "include/hode_%s.h" % name, extra + (PKG + "/csrc/hode_side_error.hpp",),
-                   lambda: [unit])
-
-
-#: every library, by file name
-LIBRARIES = {lib.name: lib for lib in (
-    Library("libhode.so", PKG + "/csrc", "include/hode.h", (), units),
-    _side("flow", PKG + "/csrc/hode_common.hpp"),   # the planar-flow posterior
-    _side("mix"),                                   # the two-model mixture CRPS
-    _side("blend"),                                 # the real-data two-model scoring kernels
-)}
-#: the libraries of the data side (the synthetic generator), same rows; kept apart from LIBRARIES, whose four names a test
-#: pins (DESIGN.md 8i: to be folded into one table by a change that may touch that test)
-DATA_LIBRARIES = {lib.name: lib for lib in (
-    _side("datagen"),                               # the synthetic data generator (DataGeneratorRoche)
-)}
-#: test-only libraries, same rows: the probe of the device helpers, compiled with the product FLAGS.  `extra` lists every
-#: header of csrc/ the unit includes, so that its digest follows an edit of a helper.
-TEST_LIBRARIES = {lib.name: lib for lib in (
-    _side("probe", *(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_lanes.hpp", "hode_lstm_kernels.hpp",
-                                                  "hode_lstm_fwd_body.hpp", "hode_lstm_bwd_body.hpp",
-                                                  "hode_neural_mf.hpp", "hode_neural_args.hpp", "hode_roche.hpp",
-                                                  "hode_host.hpp")), "include/hode.h"),
-)}
-
-
 def _neural_odd_units():
     d = os.path.join(CSRC, "neural_odd")
     return [("hode_neural_odd", os.path.join(d, "hode_neural_odd.hip"), [])] + \
         [("hode_neural_odd_d%d" % n, os.path.join(d, "hode_neural_odd_dim.hip"), ["-DHODE_DIM=%d" % n]) for n in NEURAL_ODD_DIMS]
-
-
-#: solver libraries next to libhode.so, same rows: kernels of libhode.so's templates at sizes libhode.so does not hold.
-#: `extra` lists every header of csrc/ the units include, so that the digest follows them.
-SOLVER_LIBRARIES = {lib.name: lib for lib in (
-    Library("libhode_neural_odd.so", PKG + "/csrc/neural_odd", "include/hode_neural_odd.h",
-            tuple(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_lanes.hpp", "hode_roche.hpp", "hode_host.hpp",
-                                               "hode_dopri5_kernels.hpp", "hode_neural_args.hpp", "hode_neural_mf.hpp",
-                                               "hode_neural_mf_kernels.hpp", "hode_neural_dopri5_kernels.hpp",
-                                               "hode_adaptive_host.hpp", "hode_error_state.hpp"))
-            + ("include/hode.h",), _neural_odd_units),
-)}
 
 
 def _roche_dims_units():
@@ -131,32 +65,11 @@ def _roche_dims_units():
         [("hode_roche_dims_dp_d%d" % n, os.path.join(d, "hode_roche_dims_dp_dim.hip"), ["-DHODE_DIM=%d" % n]) for n in ROCHE_DIMS]
 
 
-#: the hybrid Roche kernels at the sizes libhode.so does not hold, same rows; a table of its own because a test pins the one
-#: name of SOLVER_LIBRARIES.  `extra` lists every file of csrc/ the units include or compile from outside `src_dir`.
-ROCHE_LIBRARIES = {lib.name: lib for lib in (
-    Library("libhode_roche_dims.so", PKG + "/csrc/roche_dims", "include/hode_roche_dims.h",
-            tuple(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_lanes.hpp", "hode_roche.hpp", "hode_host.hpp",
-                                               "hode_rk_host.hpp", "hode_rk_kernels.hpp", "hode_dopri5_kernels.hpp",
-                                               "hode_adaptive_host.hpp", "hode_error_state.hpp", "hode_dopri5.hip"))
-            + ("include/hode.h",), _roche_dims_units),
-)}
-
-
 def _real_dims_units():
     d = os.path.join(CSRC, "real_dims")
     # -Wno-unused-function: hode_rk_host.hpp is included for the partial fold; its Roche argument helpers are not called here
     return [("hode_real_dims", os.path.join(d, "hode_real_dims.hip"), ["-Wno-unused-function"])] + \
         [("hode_real_dims_ht%d" % n, os.path.join(d, "hode_real_dims_ht.hip"), ["-DHODE_REAL_DIMS_HT=%d" % n]) for n in REAL_DIMS_HTS]
-
-
-#: the real-data hybrid rhs at the latent sizes libhode.so does not hold, same rows; a table of its own because tests pin the
-#: names of the other tables.  `extra` lists every file of csrc/ the units include from outside `src_dir`.
-REAL_LIBRARIES = {lib.name: lib for lib in (
-    Library("libhode_real_dims.so", PKG + "/csrc/real_dims", "include/hode_real_dims.h",
-            tuple(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_roche.hpp", "hode_host.hpp", "hode_rk_host.hpp",
-                                               "hode_error_state.hpp", "hode_real_args.hpp", "hode_real_mf.hpp"))
-            + ("include/hode.h",), _real_dims_units),
-)}
 
 
 def _lstm_seq_units():
@@ -167,46 +80,11 @@ def _lstm_seq_units():
         [("hode_lstm_seq_tpw%d" % n, os.path.join(CSRC, "hode_lstm_tpw.hip"), seq + ["-DHODE_LSTM_TPW=%d" % n]) for n in LSTM_TPWS]
 
 
-#: the LSTM kernels with the hidden state of every step as output, same rows; a table of its own because tests pin the names
-#: of the other tables.  `extra` lists every file of csrc/ the units include or compile from outside `src_dir`.
-SEQUENCE_LIBRARIES = {lib.name: lib for lib in (
-    Library("libhode_lstm_seq.so", PKG + "/csrc/lstm_seq", "include/hode_lstm_seq.h",
-            tuple(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_host.hpp", "hode_error_state.hpp",
-                                               "hode_lstm_kernels.hpp", "hode_lstm_fwd_body.hpp", "hode_lstm_bwd_body.hpp",
-                                               "hode_lstm.hip", "hode_lstm_tpw.hip"))
-            + ("include/hode.h",), _lstm_seq_units),
-)}
-
-
 def _real_step_units():
     d = os.path.join(CSRC, "real_step")
     # -Wno-unused-function: hode_rk_host.hpp is included for the partial fold; its Roche argument helpers are not called here
     return [("hode_real_step", os.path.join(d, "hode_real_step.hip"), ["-Wno-unused-function"])] + \
         [("hode_real_step_ht%d" % n, os.path.join(d, "hode_real_step_ht.hip"), ["-DHODE_REAL_STEP_HT=%d" % n]) for n in REAL_STEP_HTS]
-
-
-#: the one-step-ahead solve of the real-data hybrid rhs, same rows; a table of its own because tests pin the names of the
-#: other tables.  `extra` lists every file of csrc/ the units include from outside `src_dir`.
-STEP_LIBRARIES = {lib.name: lib for lib in (
-    Library("libhode_real_step.so", PKG + "/csrc/real_step", "include/hode_real_step.h",
-            tuple(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_roche.hpp", "hode_host.hpp", "hode_rk_host.hpp",
-                                               "hode_error_state.hpp", "hode_real_args.hpp", "hode_real_mf.hpp"))
-            + ("include/hode.h",), _real_step_units),
-)}
-
-
-#: the Sylvester flows (flow.Sylvester, flow.TriangularSylvester, flow.sylvester_chain), same rows; a table of its own because
-#: tests pin the names of the other tables.  `extra` lists every header of csrc/ the unit includes.
-FLOW_LIBRARIES = {lib.name: lib for lib in (
-    _side("sylvester", PKG + "/csrc/hode_common.hpp"),
-)}
-
-
-#: the Sylvester-flow posterior (flow.sylvester_posterior_sample, model.EncoderSylvesterLSTM), same rows; a table of its own
-#: because tests pin the names of the other tables.  `extra` lists every header of csrc/ the unit includes.
-POSTERIOR_LIBRARIES = {lib.name: lib for lib in (
-    _side("snf", PKG + "/csrc/hode_common.hpp"),
-)}
 
 
 def _dopri5_pp_units():
@@ -216,41 +94,74 @@ def _dopri5_pp_units():
         [("hode_dopri5_pp_d%d" % n, os.path.join(d, "hode_dopri5_pp_dim.hip"), ["-DHODE_DIM=%d" % n]) for n in DP_DIMS]
 
 
-#: the dopri5 solve of the hybrid Roche rhs with per-patient step control (hode.patient_dopri5, RocheODE.step_control =
-#: "patient"), same rows; a table of its own because tests pin the names of the other tables.  `extra` lists every file of
-#: csrc/ the units include from outside `src_dir`.
-ADAPTIVE_LIBRARIES = {lib.name: lib for lib in (
-    Library("libhode_dopri5_pp.so", PKG + "/csrc/dopri5_pp", "include/hode_dopri5_pp.h",
-            tuple(PKG + "/csrc/" + h for h in ("hode_common.hpp", "hode_lanes.hpp", "hode_roche.hpp", "hode_host.hpp",
-                                               "hode_rk_host.hpp", "hode_dopri5_kernels.hpp", "hode_side_error.hpp"))
-            + ("include/hode.h",), _dopri5_pp_units),
+class Library:
+    """One row of LIBRARIES: the file name of the library in hode/ and what it is built from.  `src_dir` and `header` are
+    relative to the repository root and use "/", so that digest() is the same wherever the tree lives; `units` is a callable
+    returning [(unit name, absolute source path, extra flags)]; objects go to <src_dir>/build."""
+
+    def __init__(self, name, src_dir, header, units):
+        self.name, self.src_dir, self.header, self.units = name, src_dir, header, units
+        self.out = os.path.join(ROOT, PKG, "hode", name)
+        self.obj = os.path.join(ROOT, src_dir, "build")
+
+
+def _side(name):
+    """A side library of one unit: csrc/<name>/hode_<name>.hip, with the C ABI header include/hode_<name>.h."""
+    d = PKG + "/csrc/" + name
+    unit = ("hode_" + name, os.path.join(ROOT, d, "hode_%s.hip" % name), [])
+    return Library("libhode_%s.so" % name, d, "include/hode_%s.h" % name, lambda: [unit])
+
+
+def _multi(name, units):
+    """A library of several units: sources in csrc/<name>/ (and what `units` names elsewhere), header include/hode_<name>.h."""
+    return Library("libhode_%s.so" % name, PKG + "/csrc/" + name, "include/hode_%s.h" % name, units)
+
+
+#: every library, by file name, in build order
+LIBRARIES = {lib.name: lib for lib in (
+    Library("libhode.so", PKG + "/csrc", "include/hode.h", units),  # the solvers, the LSTM, the readouts and the metrics
+    _side("flow"),                            # the planar-flow posterior
+    _side("mix"),                             # the two-model mixture CRPS
+    _side("blend"),                           # the real-data two-model scoring kernels
+    _side("datagen"),                         # the synthetic data generator (DataGeneratorRoche)
+    _side("probe"),                           # test only: the shared device helpers on their own; nothing under hode/ loads it
+    _multi("neural_odd", _neural_odd_units),  # the NeuralODE kernels at the odd latent sizes 5 .. 15, a unit per size
+    _multi("roche_dims", _roche_dims_units),  # the hybrid Roche kernels at ROCHE_DIMS, a fixed-grid and a dopri5 unit per size
+    _multi("real_dims", _real_dims_units),    # the real-data hybrid rhs at the latent sizes 5 .. 20, a unit per hidden-tile count
+    _multi("lstm_seq", _lstm_seq_units),      # the LSTM kernels with the hidden state of every step: libhode.so's units again
+    _multi("real_step", _real_step_units),    # the one-step-ahead solve of the real-data hybrid rhs, a unit per hidden-tile count
+    _side("sylvester"),                       # the chain of Sylvester flows (flow.Sylvester, flow.sylvester_chain)
+    _side("snf"),                             # the Sylvester-flow posterior with its Monte-Carlo KL (EncoderSylvesterLSTM)
+    _multi("dopri5_pp", _dopri5_pp_units),    # dopri5 of the hybrid Roche rhs with per-patient step control, a unit per DP_DIMS
 )}
-
-
-def _library(name):
-    for table in (LIBRARIES, DATA_LIBRARIES, TEST_LIBRARIES, SOLVER_LIBRARIES, ROCHE_LIBRARIES, REAL_LIBRARIES,
-                  SEQUENCE_LIBRARIES, STEP_LIBRARIES, FLOW_LIBRARIES, POSTERIOR_LIBRARIES, ADAPTIVE_LIBRARIES):
-        if name in table:
-            return table[name]
-    raise KeyError(name)
-
-
-def all_libraries():
-    return (list(LIBRARIES.values()) + list(DATA_LIBRARIES.values()) + list(TEST_LIBRARIES.values())
-            + list(SOLVER_LIBRARIES.values()) + list(ROCHE_LIBRARIES.values()) + list(REAL_LIBRARIES.values())
-            + list(SEQUENCE_LIBRARIES.values()) + list(STEP_LIBRARIES.values()) + list(FLOW_LIBRARIES.values())
-            + list(POSTERIOR_LIBRARIES.values()) + list(ADAPTIVE_LIBRARIES.values()))
-
-
 OUT = LIBRARIES["libhode.so"].out
 OBJ = LIBRARIES["libhode.so"].obj
+_INCLUDE = re.compile(rb'^\s*#include\s+"([^"]+)"', re.M)
+
+
+def _digest_sources(lib):
+    """{name relative to the repository root: contents} of what `lib` is built from: the ABI header, every source of
+    `src_dir`, the units' sources, and whatever these include in quotes, transitively, each name resolved against the
+    including file.  An #include under #if counts (a superset is safe); one that leaves the tree or names no file does not."""
+    lib = LIBRARIES[lib]
+    todo = [lib.src_dir + "/" + f for f in os.listdir(os.path.join(ROOT, lib.src_dir)) if f.endswith((".hpp", ".hip", ".h"))]
+    todo += [lib.header] + [os.path.relpath(s, ROOT).replace(os.sep, "/") for _, s, _ in lib.units()]
+    files = {}
+    while todo:
+        f = todo.pop()
+        if f in files:
+            continue
+        files[f] = open(os.path.join(ROOT, f), "rb").read()
+        for inc in _INCLUDE.findall(files[f]):
+            g = posixpath.normpath(posixpath.join(posixpath.dirname(f), inc.decode()))
+            if not g.startswith("../") and os.path.isfile(os.path.join(ROOT, g)):
+                todo.append(g)
+    return files
 
 
 def digest_files(lib):
-    """What digest(lib) reads, relative to the repository root: the ABI header, `extra`, every source in `src_dir`."""
-    lib = _library(lib)
-    own = [lib.src_dir + "/" + f for f in os.listdir(os.path.join(ROOT, lib.src_dir)) if f.endswith((".hpp", ".hip", ".h"))]
-    return sorted({lib.header, *lib.extra, *own})
+    """What digest(lib) reads, relative to the repository root, sorted."""
+    return sorted(_digest_sources(lib))
 
 
 def digest(lib):
@@ -258,10 +169,10 @@ def digest(lib):
     flags and the units.  Written next to the library after a build and compared by the tests and by the loader, so a
     library left over from other sources (e.g. after `git checkout`) is caught."""
     h = hashlib.sha256()
-    for f in digest_files(lib):
+    for f, text in sorted(_digest_sources(lib).items()):
         h.update(f.encode())
-        h.update(open(os.path.join(ROOT, f), "rb").read())
-    us = [(n, os.path.relpath(s, ROOT).replace(os.sep, "/"), e) for n, s, e in _library(lib).units()]
+        h.update(text)
+    us = [(n, os.path.relpath(s, ROOT).replace(os.sep, "/"), e) for n, s, e in LIBRARIES[lib].units()]
     h.update(repr((FLAGS, us)).encode())
     return h.hexdigest()
 
@@ -322,7 +233,7 @@ def link(out, objs):
 def build(jobs=7, force=False, verbose=True):
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
         futs = []
-        for lib in all_libraries():
+        for lib in LIBRARIES.values():
             os.makedirs(lib.obj, exist_ok=True)
             futs += [ex.submit(compile_one, n, s, e, force, lib.obj) for n, s, e in lib.units()]
         for f in futs:
@@ -331,7 +242,7 @@ def build(jobs=7, force=False, verbose=True):
                 print("  hipcc %-14s %.1fs" % (name, dt), flush=True)
             if verbose and err.strip():
                 print(err[-2000:], file=sys.stderr)
-    for lib in all_libraries():
+    for lib in LIBRARIES.values():
         objs = [os.path.join(lib.obj, n + ".o") for n, _, _ in lib.units()]
         if force or not os.path.exists(lib.out) or os.path.getmtime(lib.out) < max(os.path.getmtime(o) for o in objs):
             link(lib.out, objs)

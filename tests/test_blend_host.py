@@ -335,15 +335,6 @@ def test_the_binding_refuses_what_is_outside_the_domain():
         blend.horizon_sse(z(5, 0, 4), z(5, 0, 4), z(5, 0, 4), HORIZONS)
 
 
-def test_library_digest_matches_sources():
-    abi_checks.assert_digest_current("libhode_blend.so")
-
-
-def test_a_stale_library_is_refused_with_a_message(tmp_path, monkeypatch):
-    from hode import _blend_lib as BL
-    abi_checks.assert_stale_library_is_refused(BL.LIBRARY, tmp_path, monkeypatch)
-
-
 def test_every_blend_kernel_is_reached_by_a_gpu_case():
     objs = sorted(glob.glob(os.path.join(BLEND_BUILD, "*.o")))
     if not objs:

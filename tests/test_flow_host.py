@@ -212,15 +212,6 @@ def test_argument_errors_do_not_launch(flow_lib):
         assert flow_lib.hode_flow_fwd(e, None) == -2, field
 
 
-def test_library_digest_matches_sources():
-    abi_checks.assert_digest_current("libhode_flow.so")
-
-
-def test_a_stale_library_is_refused_with_a_message(tmp_path, monkeypatch):
-    from hode import _flow_lib as F
-    abi_checks.assert_stale_library_is_refused(F.LIBRARY, tmp_path, monkeypatch)
-
-
 def test_every_flow_kernel_is_reached_by_a_gpu_case():
     objs = sorted(glob.glob(os.path.join(FLOW_BUILD, "*.o")))
     if not objs:

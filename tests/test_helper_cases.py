@@ -186,26 +186,20 @@ def test_every_shared_device_helper_is_probed_or_exempt():
 
 
 def test_probe_library_is_a_test_library_only():
+    """A row of the build table like any other, with the product flags; nothing under hode/ names it."""
     import build_hip
-    assert list(build_hip.TEST_LIBRARIES) == [device_probe.FILE_NAME]
-    assert device_probe.FILE_NAME not in build_hip.LIBRARIES and device_probe.FILE_NAME not in build_hip.DATA_LIBRARIES
+    row = build_hip.LIBRARIES[device_probe.FILE_NAME]
+    assert row.header == "include/hode_probe.h" and row.src_dir == build_hip.PKG + "/csrc/probe"
+    assert [(n, os.path.relpath(s, ROOT).replace(os.sep, "/"), e) for n, s, e in row.units()] == \
+        [("hode_probe", row.src_dir + "/hode_probe.hip", [])]
     hode_dir = os.path.join(ROOT, "hybrid-ode-neurips-2021_amd", "hode")
     for fn in os.listdir(hode_dir):
         if fn.endswith(".py"):
             assert "hode_probe" not in open(os.path.join(hode_dir, fn)).read(), fn
     # the digest follows every header the unit includes
-    lib = build_hip.TEST_LIBRARIES[device_probe.FILE_NAME]
-    src = open(os.path.join(ROOT, lib.src_dir, "hode_probe.hip")).read()
+    src = open(os.path.join(ROOT, row.src_dir, "hode_probe.hip")).read()
     hashed = set(build_hip.digest_files(device_probe.FILE_NAME))
+    assert {build_hip.PKG + "/csrc/hode_common.hpp", build_hip.PKG + "/csrc/hode_lanes.hpp"} <= hashed   # the helpers it probes
     for inc in re.findall(r'#include "([^"]+)"', src):
-        rel = os.path.normpath(os.path.join(lib.src_dir, inc)).replace(os.sep, "/")
+        rel = os.path.normpath(os.path.join(row.src_dir, inc)).replace(os.sep, "/")
         assert rel in hashed, rel
-    dfile = os.path.join(lib.obj, "hode_probe.d")
-    if os.path.exists(dfile):
-        deps = {os.path.normpath(x) for x in open(dfile).read().replace("\\\n", " ").split() if not x.endswith(":")}
-        tail = os.sep + os.path.join(lib.src_dir, "hode_probe.hip")
-        roots = {d[:-len(tail)] for d in deps if d.endswith(tail)}
-        assert len(roots) == 1
-        root = roots.pop()
-        inside = {os.path.relpath(d, root).replace(os.sep, "/") for d in deps if d.startswith(root + os.sep)}
-        assert inside <= hashed, sorted(inside - hashed)

@@ -300,15 +300,6 @@ def test_argument_errors_do_not_launch(mix_lib):
     assert mix_lib.hode_mix_crps(e, None) == M.E_NULL and b"nothing to compute" in mix_lib.hode_mix_last_error_string()
 
 
-def test_library_digest_matches_sources():
-    abi_checks.assert_digest_current("libhode_mix.so")
-
-
-def test_a_stale_library_is_refused_with_a_message(tmp_path, monkeypatch):
-    from hode import _mix_lib as M
-    abi_checks.assert_stale_library_is_refused(M.LIBRARY, tmp_path, monkeypatch)
-
-
 # --------------------------------------------------------------------------------------------- kernel accounting
 def _mix_objects():
     objs = sorted(glob.glob(os.path.join(MIX_BUILD, "*.o")))

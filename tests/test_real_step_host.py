@@ -1,11 +1,9 @@
-"""CPU checks of the one-step-ahead solve's side library (no GPU): libhode_real_step.so's C ABI, digest, its row of the build
-tables, the kernels its objects contain against the GPU case table (tests/real_step_cases.py), the library's own argument
+"""CPU checks of the one-step-ahead solve's side library (no GPU): libhode_real_step.so's C ABI, its row of the build
+table, the kernels its objects contain against the GPU case table (tests/real_step_cases.py), the library's own argument
 checks, workspace layout and launch rule, the adapter that presents it under libhode.so's names, and the grid-table builder
 of hode.real_step against hode.substep.fixed_grid."""
 import glob
 import os
-import shutil
-import subprocess
 import sys
 
 import pytest
@@ -54,60 +52,14 @@ def test_sizes_agree_everywhere():
     assert "5 .. 20" in RS.sizes_text() and "1 .. 64" in RS.sizes_text() and "1 .. 8" in RS.sizes_text()
 
 
-def test_the_build_table_holds_exactly_this_library():
-    assert sorted(build_hip.STEP_LIBRARIES) == [LIB]
-    row = build_hip.STEP_LIBRARIES[LIB]
-    assert row in build_hip.all_libraries() and build_hip._library(LIB) is row
-    assert row.header == "include/hode_real_step.h" and "include/hode.h" in row.extra
-    assert row.src_dir == build_hip.PKG + "/csrc/real_step" and row.obj == os.path.join(ROOT, row.src_dir, "build")
+def test_the_row_of_the_build_table():
+    row = build_hip.LIBRARIES[LIB]
+    hashed = build_hip.digest_files(LIB)
+    assert row.header == "include/hode_real_step.h" and "include/hode.h" in hashed
+    assert row.src_dir == build_hip.PKG + "/csrc/real_step"
     want = ["hode_real_step"] + ["hode_real_step_ht%d" % n for n in cases.HTS]
     assert sorted(n for n, _, _ in row.units()) == sorted(want)
-    # the other tables keep their members
-    assert sorted(build_hip.REAL_LIBRARIES) == ["libhode_real_dims.so"] and sorted(build_hip.SEQUENCE_LIBRARIES) == ["libhode_lstm_seq.so"]
-
-
-def test_library_digest_matches_sources(lib):
-    out = build_hip.STEP_LIBRARIES[LIB].out
-    assert os.path.exists(out + ".digest"), "%s has no source digest: rebuild with `python build_hip.py`" % LIB
-    assert open(out + ".digest").read().strip() == build_hip.digest(LIB), "%s is stale: run `python build_hip.py`" % LIB
-
-
-def test_a_stale_library_is_refused_with_a_message(lib, tmp_path, monkeypatch):
-    from hode import HodeConfigError, _real_step_lib as RS
-    library, out = RS.LIBRARY, build_hip.STEP_LIBRARIES[LIB].out
-    assert library.check_digest
-    monkeypatch.setattr(library, "handle", None)
-    monkeypatch.setattr(library, "directory", str(tmp_path))
-    with pytest.raises(HodeConfigError, match="not found"):
-        library.load()
-    shutil.copy(out, tmp_path / LIB)
-    (tmp_path / (LIB + ".digest")).write_text("0" * 64 + "\n")
-    with pytest.raises(HodeConfigError, match="stale"):
-        library.load()
-    shutil.copy(out + ".digest", tmp_path / (LIB + ".digest"))
-    assert library.load().hode_real_step_version() == library.abi_version
-
-
-def _includes(path, seen):
-    """Every file of the tree `path` includes, transitively (quoted includes, resolved against the including file)."""
-    import re
-    for inc in re.findall(r'^\s*#include\s+"([^"]+)"', open(path).read(), flags=re.M):
-        f = os.path.normpath(os.path.join(os.path.dirname(path), inc))
-        if f not in seen and os.path.exists(f):
-            seen.add(f)
-            _includes(f, seen)
-    return seen
-
-
-def test_extra_lists_every_header_the_units_include():
-    row = build_hip.STEP_LIBRARIES[LIB]
-    hashed = set(build_hip.digest_files(LIB))
-    included = set()
-    for _, src, _ in row.units():
-        included |= {os.path.relpath(f, ROOT).replace(os.sep, "/") for f in _includes(src, {src})}
-    assert build_hip.PKG + "/csrc/hode_real_mf.hpp" in included and build_hip.PKG + "/csrc/hode_rk_host.hpp" in included
-    assert included <= hashed, sorted(included - hashed)
-    assert set(row.extra) <= included | {"include/hode.h"}, sorted(set(row.extra) - included)   # and nothing it does not
+    assert build_hip.PKG + "/csrc/hode_real_mf.hpp" in hashed and build_hip.PKG + "/csrc/hode_rk_host.hpp" in hashed
 
 
 def test_the_device_code_is_shared_not_copied():
@@ -131,7 +83,7 @@ def test_the_device_code_is_shared_not_copied():
 
 
 def test_every_compiled_kernel_is_reached_by_a_gpu_case():
-    row = build_hip.STEP_LIBRARIES[LIB]
+    row = build_hip.LIBRARIES[LIB]
     objs = sorted(glob.glob(os.path.join(row.obj, "*.o")))
     if not objs:
         build_hip.build(verbose=False)
@@ -164,12 +116,6 @@ def test_the_case_table_holds_what_it_promises():
     assert all(c["S"] == 1 for c in cases.COMPARE_CASES) and {c["method"] for c in cases.COMPARE_CASES} == set(cases.METHODS)
     assert {c["D"] == 20 for c in cases.COMPARE_CASES} == {True, False}
     assert cases.MODEL_DIMS == (7, 20) and cases.MODEL_STEP_DIVS == (1, 2)
-
-
-def test_importing_the_package_does_not_load_the_library():
-    code = ("import sys; sys.path[:0] = %r; import hode, model; from hode import real, real_step, _real_step_lib as RS; "
-            "assert RS.LIBRARY.handle is None; print('ok')" % [ROOT, os.path.join(ROOT, build_hip.PKG)])
-    assert subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True).stdout.strip() == "ok"
 
 
 # ------------------------------------------------------------------------------------------------ 2. the library's checks

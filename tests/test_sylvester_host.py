@@ -1,15 +1,12 @@
 """CPU checks of the Sylvester flows (no GPU): the mirror modules (flow.Sylvester, flow.TriangularSylvester,
 flow.sylvester_chain) against the reference's own numbers (G19, tests/golden/make_golden_sylvester.py), the float64
-restatement (sylvester_eager) against G19, the two reproduced quirks, libhode_sylvester.so's C ABI, build-table row,
-digest and loader messages, the compiled kernels against the GPU case table (tests/sylvester_cases.py), and the domain
+restatement (sylvester_eager) against G19, the two reproduced quirks, libhode_sylvester.so's C ABI and build-table row,
+the compiled kernels against the GPU case table (tests/sylvester_cases.py), and the domain
 refusals."""
 import glob
-import importlib.util
 import os
 import re
-import shutil
 import struct
-import subprocess
 import sys
 
 import numpy as np
@@ -218,68 +215,15 @@ def test_struct_layout_matches_the_c_header(tmp_path):
     assert SL.new_desc().struct_size == __import__("ctypes").sizeof(SL.SylvesterDesc)
 
 
-def test_the_build_table_holds_exactly_this_library():
-    assert sorted(build_hip.FLOW_LIBRARIES) == [LIB]
-    row = build_hip.FLOW_LIBRARIES[LIB]
-    assert row in build_hip.all_libraries() and build_hip._library(LIB) is row
-    assert row.header == "include/hode_sylvester.h"
-    assert row.src_dir == build_hip.PKG + "/csrc/sylvester" and row.obj == os.path.join(ROOT, row.src_dir, "build")
+def test_the_row_of_the_build_table():
+    row = build_hip.LIBRARIES[LIB]
+    assert row.header == "include/hode_sylvester.h" and row.src_dir == build_hip.PKG + "/csrc/sylvester"
     assert [(n, os.path.relpath(s, ROOT).replace(os.sep, "/"), e) for n, s, e in row.units()] == \
         [("hode_sylvester", row.src_dir + "/hode_sylvester.hip", [])]
-    assert row.out == os.path.join(ROOT, build_hip.PKG, "hode", LIB)
-    # the other tables keep their members
-    assert LIB not in build_hip.LIBRARIES and sorted(build_hip.STEP_LIBRARIES) == ["libhode_real_step.so"]
-    assert len({lib.name for lib in build_hip.all_libraries()}) == len(build_hip.all_libraries())
-
-
-def test_library_digest_matches_sources(lib):
-    out = build_hip.FLOW_LIBRARIES[LIB].out
-    assert os.path.exists(out + ".digest"), "%s has no source digest: rebuild with `python build_hip.py`" % LIB
-    assert open(out + ".digest").read().strip() == build_hip.digest(LIB), "%s is stale: run `python build_hip.py`" % LIB
-
-
-def test_digest_does_not_depend_on_the_location_of_the_tree(tmp_path):
-    shutil.copy(os.path.join(ROOT, "build_hip.py"), tmp_path / "build_hip.py")
-    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "include")
-    shutil.copytree(build_hip.CSRC, tmp_path / build_hip.PKG / "csrc", ignore=shutil.ignore_patterns("build"))
-    spec = importlib.util.spec_from_file_location("_build_hip_copy_sylvester", str(tmp_path / "build_hip.py"))
-    copy = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(copy)
-    assert copy.ROOT == str(tmp_path) != ROOT
-    assert copy.digest(LIB) == build_hip.digest(LIB) and copy.digest_files(LIB) == build_hip.digest_files(LIB)
-    # and it follows the sources: one more byte in the unit changes it
-    with open(tmp_path / build_hip.PKG / "csrc" / "sylvester" / "hode_sylvester.hip", "a") as f:
-        f.write("\n")
-    assert copy.digest(LIB) != build_hip.digest(LIB)
-
-
-def _includes(path, seen):
-    """Every file of the tree `path` includes, transitively (quoted includes, resolved against the including file)."""
-    for inc in re.findall(r'^\s*#include\s+"([^"]+)"', open(path).read(), flags=re.M):
-        f = os.path.normpath(os.path.join(os.path.dirname(path), inc))
-        if f not in seen and os.path.exists(f):
-            seen.add(f)
-            _includes(f, seen)
-    return seen
-
-
-def test_extra_lists_every_header_the_unit_includes():
-    row = build_hip.FLOW_LIBRARIES[LIB]
-    hashed = set(build_hip.digest_files(LIB))
-    (_, src, _), = row.units()
-    included = {os.path.relpath(f, ROOT).replace(os.sep, "/") for f in _includes(src, {src})}
-    assert {build_hip.PKG + "/csrc/hode_common.hpp", build_hip.PKG + "/csrc/hode_side_error.hpp", "include/hode_sylvester.h"} <= included
-    assert included <= hashed, sorted(included - hashed)
-    assert set(row.extra) <= included, sorted(set(row.extra) - included)   # and nothing it does not
-    dfile = os.path.join(row.obj, "hode_sylvester.d")
-    if os.path.exists(dfile):   # what hipcc really read
-        deps = {os.path.normpath(x) for x in open(dfile).read().replace("\\\n", " ").split() if not x.endswith(":")}
-        tail = os.sep + os.path.relpath(src, ROOT)
-        roots = {d[:-len(tail)] for d in deps if d.endswith(tail)}
-        assert len(roots) == 1
-        root = roots.pop()
-        inside = {os.path.relpath(d, root).replace(os.sep, "/") for d in deps if d.startswith(root + os.sep)}
-        assert inside and inside <= hashed, sorted(inside - hashed)
+    assert {build_hip.PKG + "/csrc/hode_common.hpp", build_hip.PKG + "/csrc/hode_side_error.hpp",
+            "include/hode_sylvester.h"} <= set(build_hip.digest_files(LIB))
+    from hode import _sylvester_lib as SL
+    assert SL.LIBRARY.noun.startswith("the Sylvester flows")   # what the loader says has no CPU fallback
 
 
 def test_new_device_helpers_stay_in_the_unit():
@@ -289,30 +233,8 @@ def test_new_device_helpers_stay_in_the_unit():
     assert sorted(f for f in os.listdir(os.path.join(build_hip.CSRC, "sylvester")) if f != "build") == ["hode_sylvester.hip"]
 
 
-def test_a_missing_and_a_stale_library_are_refused_with_a_message(lib, tmp_path, monkeypatch):
-    from hode import HodeConfigError, _sylvester_lib as SL
-    library, out = SL.LIBRARY, build_hip.FLOW_LIBRARIES[LIB].out
-    assert library.check_digest and library.file_name == LIB and library.env == "HODE_SYLVESTER_LIBRARY"
-    monkeypatch.setattr(library, "handle", None)
-    monkeypatch.setattr(library, "directory", str(tmp_path))
-    with pytest.raises(HodeConfigError, match=r"libhode_sylvester\.so not found -- build it with `python build_hip\.py`.*no CPU fallback for the Sylvester flows"):
-        library.load()
-    shutil.copy(out, tmp_path / LIB)
-    (tmp_path / (LIB + ".digest")).write_text("0" * 64 + "\n")
-    with pytest.raises(HodeConfigError, match=r"libhode_sylvester\.so is stale .*rebuild with `python build_hip\.py`"):
-        library.load()
-    shutil.copy(out + ".digest", tmp_path / (LIB + ".digest"))
-    assert library.load().hode_sylvester_version() == library.abi_version
-
-
-def test_importing_the_package_does_not_load_the_library():
-    code = ("import sys; sys.path[:0] = %r; import hode, flow; from hode import sylvester, _sylvester_lib as SL; "
-            "assert SL.LIBRARY.handle is None; print('ok')" % [ROOT, os.path.join(ROOT, build_hip.PKG)])
-    assert subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True).stdout.strip() == "ok"
-
-
 def test_every_compiled_kernel_is_reached_by_a_gpu_case():
-    row = build_hip.FLOW_LIBRARIES[LIB]
+    row = build_hip.LIBRARIES[LIB]
     objs = sorted(glob.glob(os.path.join(row.obj, "*.o")))
     if not objs:
         pytest.skip("object files are not in the tree (library shipped pre-built)")
@@ -329,7 +251,7 @@ def test_every_compiled_kernel_is_reached_by_a_gpu_case():
 
 
 def test_no_compiled_kernel_uses_scratch():
-    row = build_hip.FLOW_LIBRARIES[LIB]
+    row = build_hip.LIBRARIES[LIB]
     objs = sorted(glob.glob(os.path.join(row.obj, "*.o")))
     if not objs:
         pytest.skip("object files are not in the tree (library shipped pre-built)")
