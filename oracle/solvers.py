@@ -261,6 +261,7 @@ def _odeint_dopri5(func, y0, t, rtol, atol, max_num_steps=2 ** 31 - 1, stats=Non
     out = [y0]
     n_acc = n_rej = 0
     tape = []
+    states, attempts = [], []  # stats only: the start state of every accepted step; (accepted so far, t, dt, ratio) per attempt
     first_ok = False
     for j in range(1, len(t)):
         n_steps = 0
@@ -272,11 +273,15 @@ def _odeint_dopri5(func, y0, t, rtol, atol, max_num_steps=2 ** 31 - 1, stats=Non
             y1, f1, err, k = _dp_attempt(f, y, fy, t_hi, dt, t_new, tab)
             tol = atol + rtol * torch.max(y.abs(), y1.abs())
             ratio = _rms(err / tol).abs()
+            if stats is not None:
+                attempts.append((n_acc, float(t_hi.detach()), float(dt.detach()), float(ratio.detach())))
             if ratio <= 1:
                 coef = _interp_fit(y, y1, k, dt, c_mid)
                 if not tape:
                     first_ok = n_rej == 0
                 tape.append((float(t_hi.detach()), float(dt.detach())))
+                if stats is not None:
+                    states.append(y.detach().clone())
                 t_lo, t_hi = t_hi, t_new
                 y, fy = y1, f1
                 n_acc += 1
@@ -287,7 +292,8 @@ def _odeint_dopri5(func, y0, t, rtol, atol, max_num_steps=2 ** 31 - 1, stats=Non
             n_steps += 1
         out.append(_interp_eval(coef, t_lo, t_hi, t[j]))
     if stats is not None:
-        stats.update(n_accepted=n_acc, n_rejected=n_rej, nfe=f.nfe, tape=tape, first_attempt_accepted=first_ok)
+        stats.update(n_accepted=n_acc, n_rejected=n_rej, nfe=f.nfe, tape=tape, first_attempt_accepted=first_ok,
+                     states=states, attempts=attempts)
     return torch.stack(out, dim=0)
 
 

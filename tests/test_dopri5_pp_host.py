@@ -1,7 +1,9 @@
 """CPU checks of the per-patient dopri5 path (no GPU): libhode_dopri5_pp.so's C ABI and build-table row,
 the compiled kernels against the GPU case table (tests/dopri5_pp_cases.py), the library's own refusals, the
 refusals that happen before anything is loaded, and the dispatch from hode.odeint / model.RocheODE.step_control."""
+import copy
 import ctypes
+import functools
 import glob
 import os
 import sys
@@ -11,6 +13,7 @@ import torch
 
 import abi_checks
 import build_hip
+import dopri5_pp_audit as audit
 import dopri5_pp_cases as cases
 import kernel_variants as kv
 import model
@@ -87,6 +90,7 @@ def test_every_compiled_kernel_is_reached_by_a_gpu_case():
     want = cases.all_kernels() | {"hode::fold_partials_kernel"}
     assert compiled == want, (sorted(compiled - want), sorted(want - compiled))
     assert set().union(*(cases.kernels(c) for c in cases.CASES)) == cases.all_kernels()
+    assert set().union(*(cases.kernels(c) for c in cases.CASES + cases.GRID_CASES)) == cases.all_kernels()
     assert len(cases.all_kernels()) == 24
 
 
@@ -306,3 +310,187 @@ def test_the_autograd_function_lives_next_to_the_module_it_serves():
     assert not [b for b in found if b.startswith(("patient_dopri5.", "_dopri5_pp_lib."))], found
     assert issubclass(model._RochePatientDopri5, torch.autograd.Function)
     assert not cov.pointer_problems()
+
+
+# ------------------------------------------------------------------------------------- 6. the grid cases' table
+def test_the_grid_table_holds_what_the_issue_lists():
+    gs = cases.GRID_CASES
+    assert {c["grid"] for c in gs} == set(cases.GRIDS) and all(c["T"] == cases.GRID_T == 12 for c in gs)
+    assert {c["B"] for c in gs} == {1, 3, 70} and {c["K"] for c in gs} == {1, 2, 3}
+    for g in cases.GRIDS:
+        on = [c for c in gs if c["grid"] == g]
+        assert {c["D"] for c in on} == set(cases.DIMS), g
+        assert any(c["ablate"] for c in on) and any(c["hill"] == "general" for c in on) and any(not c["need_theta"] for c in on), g
+    assert {cases.bodies(c) for c in gs} == {cases.bodies(c) for c in cases.CASES} == {(True, True), (True, False), (False, False)}
+    ids = list(map(cases.case_id, cases.CASES + gs))
+    assert len(set(ids)) == len(ids) and len(gs) <= 18
+    assert len(set(map(cases.audit_id, cases.AUDIT_CASES))) == len(cases.AUDIT_CASES)
+
+
+def test_grid_case_inputs_are_time_grids_own_and_hold_the_doses_they_name():
+    import time_grids as tg
+    from oracle.rhs import THETA_NAMES
+    for c in cases.GRID_CASES + cases.AUDIT_CASES:
+        inp, f = cases.setup(c)
+        p = tg._roche_inputs(c["D"], c["ablate"], c["K"], c["grid"], c["T"])
+        B, rows = c["B"], slice(c["first"], c["first"] + c["B"])
+        assert torch.equal(inp["t"], tg.grid(c["grid"], 12)) and torch.equal(inp["times"], p["times"][rows]) and inp["times"].shape == (B, c["K"])
+        assert torch.equal(inp["dosage"], p["dosage"][rows])  # a quarter of synth's amounts, as time_grids takes them
+        if "stiff" not in c:
+            assert torch.equal(inp["z0"], p["y0"][rows])
+        assert f.ablate == c["ablate"] and (float(f.HillCure) == 2.0) == (c["hill"] == "two")
+        if c["hill"] == "general":
+            assert [float(getattr(f, n)) for n in THETA_NAMES] == [pytest.approx(v) for v in cases.THETA_GENERAL]
+        t0, S = float(inp["t"][0]), cases.subset(B)
+        inside = [x for x in inp["times"].double().flatten().tolist() if x not in inp["t"].double().tolist() and x > t0]
+        assert inside or B == 1, cases.case_id(c)  # doses strictly inside grid steps
+        if c["grid"] != "clustered":  # among the replayed patients: a dose before t[0] and a dose exactly on it
+            assert bool((inp["times"][S] == t0 - tg.BEFORE).any()) and bool((inp["times"][S] == t0).any()), cases.case_id(c)
+    assert float(tg.grid("offset-", 12)[0]) < 0 < float(tg.grid("offset-", 12)[-1]) and float(tg.grid("offset+", 12)[0]) == 2.5
+    # the cached problem of time_grids was not written into
+    c = cases.AUDIT_CASES[1]
+    assert "stiff" in c and float(cases.setup(c)[0]["z0"][cases.STIFF].abs().max()) > 100 * float(
+        tg._roche_inputs(c["D"], c["ablate"], c["K"], c["grid"], c["T"])["y0"][c["first"] + cases.STIFF].abs().max())
+
+
+# ------------------------------------------------------------------------------------- 7. the controller audit
+HEADROOM = 0.5  # the fp32 oracle has to pass at this share of RATIO_MARGIN and DT_RTOL (as tests/test_time_grid_cases.py)
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_runs(i):
+    """The free-running oracle at batch one, in float64 and in fp32, on every audited patient of AUDIT_CASES[i]."""
+    c = cases.AUDIT_CASES[i]
+    inp, f = cases.setup(c)
+    dosage, times = cases.schedule(inp, f)
+    out = []
+    for p in cases.subset(c["B"]):
+        run = {"p": p, "y0": inp["z0"][p], "t": inp["t"], "rhs64": audit.patient_rhs(f, dosage, times, p)}
+        _, run["st64"], run["tape64"] = audit.free_run(run["rhs64"], run["y0"], run["t"], c["rtol"], c["atol"])
+        _, run["st32"], run["tape32"] = audit.free_run(audit.patient_rhs(f, dosage, times, p, torch.float32), run["y0"], run["t"],
+                                                       c["rtol"], c["atol"])
+        out.append(run)
+    return out
+
+
+def _audit(c, run, tape, n_rejected, share=1.0):
+    return audit.audit(run["rhs64"], run["y0"], run["t"], c["rtol"], c["atol"], tape, n_rejected, share * cases.RATIO_MARGIN,
+                       share * cases.DT_RTOL)
+
+
+def test_the_audit_table_holds_what_the_issue_lists():
+    cs = cases.AUDIT_CASES
+    assert 8 <= len(cs) <= 10 and all(c["B"] == 70 and not c["ablate"] for c in cs)
+    assert {c["grid"] for c in cs} == set(cases.GRIDS) and {c["D"] for c in cs} >= {4, 12} and {c["D"] for c in cs} & {6, 8}
+    tols = {(c["rtol"], c["atol"]) for c in cs}
+    assert len(tols) == 2 and (cases.RTOL, cases.ATOL) not in tols and len({r / a for r, a in tols}) == 2
+    assert all(r != a for r, a in tols)  # swapping the two changes the problem
+    assert any("stiff" in c for c in cs) and all(c["stiff"][0] == cases.STIFF in cases.subset(70) for c in cs if "stiff" in c)
+    assert cases.RATIO_MARGIN == 8 * cases.MEASURED_RATIO_DIST and cases.DT_RTOL == 8 * cases.MEASURED_DT_DIST
+
+
+@pytest.mark.parametrize("i", range(len(cases.AUDIT_CASES)), ids=[cases.audit_id(c) for c in cases.AUDIT_CASES])
+def test_the_float64_oracle_decides_every_attempt_and_the_fp32_oracle_passes_the_audit(i, record_property):
+    """The inputs were chosen so that the float64 oracle, free-running, has no attempt whose ratio is within RATIO_MARGIN of
+    1 on any audited patient (so no patient is undecidable before fp32 comes in), and its own tape passes the audit.  The
+    fp32 oracle -- the stand-in for the device the two constants were measured on -- stays within HEADROOM of both, and its
+    tape passes the audit at HEADROOM of both."""
+    c = cases.AUDIT_CASES[i]
+    worst = {"ratio": 0.0, "dt": 0.0}
+    for run in _oracle_runs(i):
+        clear = min(abs(r - 1.0) / max(1.0, r) for _, _, _, r in run["st64"]["attempts"])
+        assert clear > cases.RATIO_MARGIN, (run["p"], clear)
+        rep = _audit(c, run, run["tape64"], run["st64"]["n_rejected"])
+        assert rep["ok"] and not rep["left_out"], (run["p"], rep)
+        dist = max(audit.ratio_distances(run["rhs64"], run["t"], c["rtol"], c["atol"], run["st32"]))
+        rep = _audit(c, run, run["tape32"], run["st32"]["n_rejected"], HEADROOM)
+        assert rep["ok"] and not rep["left_out"], (run["p"], rep)
+        worst["ratio"], worst["dt"] = max(worst["ratio"], dist, rep["ratio_dist"]), max(worst["dt"], rep["dt_dist"])
+    record_property("fp32_oracle_ratio_dist", worst["ratio"])
+    record_property("fp32_oracle_dt_dist", worst["dt"])
+    assert worst["ratio"] <= HEADROOM * cases.RATIO_MARGIN and worst["dt"] <= HEADROOM * cases.DT_RTOL, worst
+
+
+def test_the_audited_inputs_exercise_the_controller():
+    """On the oracle's counts: patients reject, take different numbers of steps, the scaled patients' first attempt is
+    rejected, some audited patient's rejected count is held exactly and is not zero, most steps' proposals are followed
+    through, and on the clustered grid one step covers at least 3 output times while at least 2 cover none."""
+    import time_grids as tg
+    exact, steps, open_steps = [], 0, 0
+    for i, c in enumerate(cases.AUDIT_CASES):
+        runs = _oracle_runs(i)
+        counts = [(r["st32"]["n_accepted"], r["st32"]["n_rejected"]) for r in runs]
+        assert len({a for a, _ in counts}) > 1 and any(b > 0 for _, b in counts), (cases.audit_id(c), counts)
+        for run in runs:
+            if "stiff" in c and run["p"] == cases.STIFF:
+                assert not run["st32"]["first_attempt_accepted"] and not run["st64"]["first_attempt_accepted"]
+            elif c["grid"] == "clustered":
+                cover = tg.outputs_per_step(run["st32"]["tape"], run["t"].numpy())
+                assert max(cover) >= 3 and sum(1 for n in cover if n == 0) >= 2, (cases.audit_id(c), run["p"], cover)
+            rep = _audit(c, run, run["tape32"], run["st32"]["n_rejected"])
+            steps, open_steps = steps + rep["steps"], open_steps + rep["open_steps"]
+            if rep["exact"]:
+                exact.append(rep["n_rejected"])
+    assert any("stiff" in c for c in cases.AUDIT_CASES)
+    assert len(exact) >= 5 and sum(1 for n in exact if n > 0) >= 2, exact
+    assert open_steps <= 0.4 * steps, (open_steps, steps)
+
+
+def _wrong_controller(c, run, other, kind):
+    """oracle.solvers._odeint_dopri5's loop in fp32 on one patient with one thing wrong; returns (tape, n_rejected) of the
+    patient as a device would report them.  `kind`: "joint" (the norm over this patient and `other` together, count 2 D),
+    "swap" (rtol and atol swapped), "safety" (0.8 instead of 0.9), "tol_y" (tol from |y| alone), "half" (a first step of
+    0.5 x Hairer's), None (nothing wrong)."""
+    from oracle import solvers as S
+    rtol, atol = (c["atol"], c["rtol"]) if kind == "swap" else (c["rtol"], c["atol"])
+    inp, f0_ = cases.setup(c)
+    dosage, times = cases.schedule(inp, f0_)
+    rows = [run["p"], other] if kind == "joint" else [run["p"]]
+    fm = copy.deepcopy(f0_)
+    fm.dosage, fm.times = dosage[rows], times[rows]
+    f, tab, t = S._Rhs(fm), audit.tableau(torch.float32), run["t"].double()
+    with torch.no_grad():
+        y = inp["z0"][rows].clone()
+        fy = f(t[0], y)
+        dt = S._initial_step(f, t[0], y, 4, rtol, atol, fy) * (0.5 if kind == "half" else 1.0)
+        t_hi, tape, rejected = t[0], {"t": [], "dt": [], "y": []}, 0
+        while t_hi < t[-1]:
+            y1, f1, err, _ = S._dp_attempt(f, y, fy, t_hi, dt, t_hi + dt, tab)
+            tol = atol + rtol * (y.abs() if kind == "tol_y" else torch.max(y.abs(), y1.abs()))
+            ratio = S._rms(err / tol).abs()
+            if ratio <= 1:
+                tape["t"].append(float(t_hi)), tape["dt"].append(float(dt)), tape["y"].append(y[:1].clone())
+                t_hi, y, fy = t_hi + dt, y1, f1
+            else:
+                rejected += 1
+            dt = S._next_dt(dt, ratio, safety=0.8 if kind == "safety" else 0.9)
+    tape["y"] = torch.cat(tape["y"], dim=0)
+    return tape, rejected
+
+
+def test_the_restated_loop_is_the_oracles():
+    """_wrong_controller with nothing wrong gives the fp32 oracle's own tape and count, bit for bit."""
+    for i in (0, 3):
+        c = cases.AUDIT_CASES[i]
+        for run in _oracle_runs(i)[:2]:
+            tape, rejected = _wrong_controller(c, run, None, None)
+            assert tape["t"] == run["tape32"]["t"] and tape["dt"] == run["tape32"]["dt"] and rejected == run["st32"]["n_rejected"]
+            assert torch.equal(tape["y"], run["tape32"]["y"])
+
+
+#: which audited case catches which wrong controller (found on the CPU; the test below holds it)
+CAUGHT_BY = {"joint": 0, "swap": 3, "safety": 4, "tol_y": 5, "half": 2}
+
+
+@pytest.mark.parametrize("kind", sorted(CAUGHT_BY))
+def test_a_wrong_controller_fails_the_audit(kind):
+    i = CAUGHT_BY[kind]
+    c, runs = cases.AUDIT_CASES[i], _oracle_runs(i)
+    failed = []
+    for k, run in enumerate(runs):
+        tape, rejected = _wrong_controller(c, run, runs[(k + 1) % len(runs)]["p"], kind)
+        rep = _audit(c, run, tape, rejected)
+        if not rep["ok"] and not rep["left_out"]:
+            failed.append((run["p"], rep["why"]))
+    print(kind, cases.audit_id(c), failed)
+    assert failed, (kind, cases.audit_id(c))

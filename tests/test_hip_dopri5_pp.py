@@ -1,7 +1,8 @@
 """dopri5 with per-patient step control (libhode_dopri5_pp.so, hode.patient_dopri5, RocheODE.step_control = "patient") on the
-GPU: independence of the patients, every case of tests/dopri5_pp_cases.py against the float64 replay of its own tapes, the
-free-running oracle per patient, a fine fixed-grid solve, the tape-less forward, sentinels, repeats, the status paths and
-the model level.  GPU only.
+GPU: independence of the patients, every case of tests/dopri5_pp_cases.py -- synth's uniform grid and the non-uniform and
+offset grids of tests/time_grids.py -- against the float64 replay of its own tapes, the free-running oracle per patient,
+the float64 audit of the step controller at loose tolerances (tests/dopri5_pp_audit.py), a fine fixed-grid solve, the
+tape-less forward, sentinels, repeats, the status paths and the model level.  GPU only.
 
 Per-patient mode is torchdiffeq run on each patient as a batch of one, with every step size a constant in the backward
 (dt_0 included), so the references are the CPU oracle at batch one: `oracle.solvers.odeint(method="dopri5")` free-running
@@ -13,7 +14,7 @@ import pytest
 import torch
 
 import dopri5_pp_cases as cases
-from oracle.rhs import RocheRHS, THETA_NAMES, dose_schedule
+from oracle.rhs import RocheRHS, THETA_NAMES
 from oracle.solvers import odeint as oracle_odeint, odeint_dopri5_replay
 
 pytestmark = pytest.mark.gpu
@@ -40,25 +41,39 @@ def _device_args(inp, f, dev):
     """(y0, theta, w, b, t, dosage, dose_times) on the device, as the launch functions take them."""
     from hode.solver import pack_theta
     scal = [getattr(f, n).detach().to(dev) for n in _names(f)]
-    dosage, times = dose_schedule(inp["actions"], f.step_size)
+    dosage, times = cases.schedule(inp, f)
     w = f.ml_net[0].weight.detach().to(dev) if f.ml_dim > 0 else None
     b = f.ml_net[0].bias.detach().to(dev) if f.ml_dim > 0 else None
     return (inp["z0"].to(dev), pack_theta(scal, dev), w, b, inp["t"].to(dev), dosage.to(dev), times.to(dev))
 
 
-def _solve(inp, f, dev, cot=None, need_theta=True, **kw):
+def _tape_states(ws, B, D, max_steps, n_acc):
+    """The fp32 start state of every accepted step, per patient, out of a forward's workspace: tape_y is
+    [max_steps][B][D] at the last offset hode_dopri5_pp_tape_offsets reports."""
+    from hode import _dopri5_pp_lib as PL
+    d = PL.new_desc()
+    d.batch, d.latent_dim, d.n_times, d.n_dose, d.max_steps = B, D, 1, 1, int(max_steps)
+    off = (ctypes.c_size_t * 5)()
+    PL.check(PL.lib().hode_dopri5_pp_tape_offsets(d, off), "hode_dopri5_pp_tape_offsets")
+    assert off[4] % 4 == 0 and off[4] // 4 + max_steps * B * D <= ws.numel()
+    y = ws[off[4] // 4:off[4] // 4 + max_steps * B * D].cpu().view(torch.float32).reshape(max_steps, B, D)
+    return [y[:n, p].clone() for p, n in enumerate(n_acc.cpu().tolist())]
+
+
+def _solve(inp, f, dev, cot=None, need_theta=True, rtol=RTOL, atol=ATOL, **kw):
     """Forward (+ backward when `cot` is given) through the two launch functions; everything comes back on the CPU."""
     from hode import patient_dopri5 as PP
     args = _device_args(inp, f, dev)
-    h, ws, stats = PP.patient_dopri5_forward(*args, rtol=RTOL, atol=ATOL, ablate=f.ablate, **kw)
+    h, ws, stats = PP.patient_dopri5_forward(*args, rtol=rtol, atol=atol, ablate=f.ablate, **kw)
     B, D = inp["z0"].shape
     out = {"h": h.cpu(), "n_acc": stats["n_accepted"].cpu(), "n_rej": stats["n_rejected"].cpu(), "status": stats["status"].cpu(),
            "max_steps": stats["max_steps"], "workspace_bytes": stats["workspace_bytes"], "ws": ws}
     if not kw.get("no_tape"):
         out["tapes"] = PP.read_tape(ws, B, D, stats["max_steps"], stats["n_accepted"])
+        out["tape_y"] = _tape_states(ws, B, D, stats["max_steps"], stats["n_accepted"])
     if cot is not None:
-        gy0, gth, gw, gb = PP.patient_dopri5_backward(*args, h, ws, stats["n_accepted"], stats["max_steps"], cot.to(dev), rtol=RTOL,
-                                                      atol=ATOL, ablate=f.ablate, need_theta=need_theta)
+        gy0, gth, gw, gb = PP.patient_dopri5_backward(*args, h, ws, stats["n_accepted"], stats["max_steps"], cot.to(dev), rtol=rtol,
+                                                      atol=atol, ablate=f.ablate, need_theta=need_theta)
         out["gy0"] = gy0.cpu()
         if gth is not None:
             out["gtheta"] = gth.cpu()[:len(_names(f))]
@@ -76,10 +91,9 @@ def _replay(inp, f, cot, tapes, patients, double):
     for p_ in fm.parameters():
         p_.grad = None
     hs, gy = [], []
+    dosage, times = cases.schedule(inp, f)
     for p in patients:
-        fm.set_action(inp["actions"][:, p:p + 1])
-        if double:
-            fm.dosage, fm.times = fm.dosage.double(), fm.times.double()
+        fm.dosage, fm.times = dosage[p:p + 1].to(dt), times[p:p + 1].to(dt)
         y0 = inp["z0"][p:p + 1].to(dt).clone().requires_grad_(True)
         tape = tapes[p]
         h = odeint_dopri5_replay(fm, y0, inp["t"].to(dt), RTOL, ATOL, list(zip(tape["t"], tape["dt"])), False)
@@ -95,8 +109,8 @@ def _replay(inp, f, cot, tapes, patients, double):
 
 
 # --------------------------------------------------------------------------------------- 2. tape replay, every case
-@pytest.mark.parametrize("case", cases.CASES, ids=cases.case_id)
-def test_every_case_follows_the_float64_replay_of_its_own_tapes(case):
+@pytest.mark.parametrize("case", cases.CASES + cases.GRID_CASES, ids=cases.case_id)
+def test_every_case_follows_the_float64_replay_of_its_own_tapes(case, record_property):
     """Every compiled instantiation (tests/test_dopri5_pp_host.py holds the table against the library's symbols).  The
     cotangent is non-zero on the patients of cases.subset(B) -- all of them up to B = 5, else both ends of both waves -- so
     that the float64 replay of exactly those patients gives the h rows, the grad_y0 rows and the parameter gradients summed
@@ -108,7 +122,13 @@ def test_every_case_follows_the_float64_replay_of_its_own_tapes(case):
 
     Measured on an MI355X over the 21 cases that integrate: |h - h64| at most 5.1e-6 (the bound is at least 2e-5); gradient
     distances 5.5e-8 .. 2.0e-6 with the fp32 oracle replay at 3.3e-8 .. 2.3e-6 from the fp64 one, i.e. at most 0.2 of the
-    bound."""
+    bound.
+
+    GRID_CASES: the same on the clustered grid (one accepted step covers several output times -- the forward's inner j loop
+    and the sweep's sum over several grad_h rows -- and many cover none: empty tape_j ranges) and on the grids that start at
+    2.5 and at -1.0 and cross 0 (nextafter_down of a negative t0f), with a dose before t[0], on t[0] and strictly inside
+    grid steps, up to three per patient.  Measured over these 16 cases: |h - h64| at most 1.5e-6, gradient distances
+    5.1e-8 .. 9.3e-7 with the fp32 oracle replay at 9.0e-8 .. 2.5e-6, at most 0.09 of the bound."""
     dev = _dev()
     inp, f = cases.setup(case)
     B, D, T = case["B"], case["D"], case["T"]
@@ -124,9 +144,19 @@ def test_every_case_follows_the_float64_replay_of_its_own_tapes(case):
             assert k not in hip or not hip[k].any()
         return
     assert int(hip["n_acc"].min()) >= 1 and all(len(tp["t"]) == int(n) for tp, n in zip(hip["tapes"], hip["n_acc"]))
+    t64 = inp["t"].double().tolist()
     for tp in hip["tapes"]:  # every tape starts at t[0], is contiguous in time and hands out every output index once
-        assert tp["t"][0] == 0.0 and all(a + b == c for a, b, c in zip(tp["t"], tp["dt"], tp["t"][1:]))
+        assert tp["t"][0] == float(inp["t"][0]) and all(a + b == c for a, b, c in zip(tp["t"], tp["dt"], tp["t"][1:]))
         assert tp["j"][0][0] == 1 and tp["j"][-1][1] == T and all(a[1] == b[0] for a, b in zip(tp["j"], tp["j"][1:]))
+        # and a step's range is exactly the output times inside (t_n, t_n + dt_n]
+        assert all(all(a < t64[j] <= a + b for j in range(lo, hi)) and (hi == T or t64[hi] > a + b)
+                   for a, b, (lo, hi) in zip(tp["t"], tp["dt"], tp["j"]))
+    if case.get("grid") == "clustered":  # one accepted step covers several output times, several cover none
+        widths = [[hi - lo for lo, hi in hip["tapes"][p]["j"]] for p in S]
+        assert max(map(max, widths)) >= 3 and all(sum(1 for w in ws if w == 0) >= 2 for ws in widths), widths
+    elif "grid" in case:  # from the inputs: a replayed patient with a dose before t[0] and one with a dose exactly on it
+        times = inp["times"][S]
+        assert bool((times < inp["t"][0]).any()) and bool((times == inp["t"][0]).any())
     r64 = _replay(inp, f, cot, hip["tapes"], S, True)
     r32 = _replay(inp, f, cot, hip["tapes"], S, False)
     scale = 1 + r64["h"].abs().max().item()
@@ -143,6 +173,11 @@ def test_every_case_follows_the_float64_replay_of_its_own_tapes(case):
             continue
         figures[k] = (_rel(got, r64[k]), _rel(r32[k], r64[k]))
         print("  %s: rel %.3e, fp32 oracle %.3e" % ((k,) + figures[k]))
+    record_property("err_h", herr)
+    record_property("err_h_bound", 2e-5 * scale)
+    for k, (err, noise) in figures.items():
+        record_property("err_" + k, err)
+        record_property("fp32_oracle_" + k, noise)
     assert herr <= 2e-5 * scale
     assert not hip["gy0"][others].any()
     for k, (err, noise) in figures.items():
@@ -216,6 +251,52 @@ def test_forward_against_the_free_running_oracle_per_patient(D):
     assert int(hip["n_rej"][STIFF]) > 0 and first["t"][0] == 0.0
 
 
+# ------------------------------------------------------------------------------------------ 3b. the controller audit
+@pytest.mark.parametrize("case", cases.AUDIT_CASES, ids=cases.audit_id)
+def test_the_controller_follows_the_float64_controller(case, record_property):
+    """WHICH steps are taken (the replay above checks the algebra given the steps): tests/dopri5_pp_audit.py re-runs
+    torchdiffeq's controller in float64 from the kernel's own (t_n, y_n) of every accepted step -- Hairer's first step, the
+    RMS norm over the patient's D components, atol + rtol * max(|y|, |y1|), accept / reject, 0.9 ratio^(-1/5) with its
+    clamps -- at tolerances where the error estimate is more than roundoff, on non-uniform grids with doses inside steps.
+    Every accepted dt has to lie where float64's controller, with ratios within RATIO_MARGIN of its own, puts it (within
+    DT_RTOL), float64 has to accept every step of the tape, and the rejected count has to be float64's.  Both constants
+    are 8 x what the fp32 oracle shows when it is audited the same way (tests/dopri5_pp_cases.py;
+    tests/test_dopri5_pp_host.py shows that a norm over the wrong count, swapped tolerances, a safety factor of 0.8, a
+    tolerance from |y| alone and half of Hairer's step each fail this audit).  At most one audited patient in ten may be
+    undecidable, i.e. none of five.
+
+    Measured on an MI355X over the 45 audited patients: none undecidable, every dt inside its interval with the largest
+    distance 4.6e-5 (DT_RTOL 5.4e-3), the ratios that dt_n / dt_{n-1} names within 5.1e-5 of float64's (RATIO_MARGIN
+    7.0e-4); the two scaled-up patients take 42 / 39 steps with 10 / 6 rejections, float64's counts exactly."""
+    import dopri5_pp_audit as audit
+    dev = _dev()
+    inp, f = cases.setup(case)
+    B, S = case["B"], cases.subset(case["B"])
+    hip = _solve(inp, f, dev, rtol=case["rtol"], atol=case["atol"])
+    assert not hip["status"].any() and torch.isfinite(hip["h"]).all()
+    dosage, times = cases.schedule(inp, f)
+    left_out, worst = [], {"dt": 0.0, "ratio": 0.0}
+    for p in S:
+        tape = dict(hip["tapes"][p], y=hip["tape_y"][p])
+        rep = audit.audit(audit.patient_rhs(f, dosage, times, p), inp["z0"][p], inp["t"], case["rtol"], case["atol"], tape,
+                          int(hip["n_rej"][p]), cases.RATIO_MARGIN, cases.DT_RTOL)
+        print("patient %d: %d accepted, %d rejected (float64 %s%d), %d of %d steps open, dt distance %.3e, ratio distance %.3e, "
+              "clearance %.3e %s" % (p, int(hip["n_acc"][p]), int(hip["n_rej"][p]), "" if rep.get("exact") else ">= ", rep["n_rejected"],
+                                    rep["open_steps"], rep["steps"], rep["dt_dist"], rep["ratio_dist"], rep["clearance"], rep["why"]))
+        worst["dt"], worst["ratio"] = max(worst["dt"], rep["dt_dist"]), max(worst["ratio"], rep["ratio_dist"])
+        if rep["left_out"]:
+            left_out.append(p)
+        else:
+            assert rep["ok"], (p, rep["why"])
+    record_property("audit_dt_dist", worst["dt"])
+    record_property("audit_ratio_dist", worst["ratio"])
+    record_property("left_out", len(left_out))
+    assert 10 * len(left_out) <= len(S), left_out
+    if "stiff" in case:  # the scaled patient's first attempt is rejected: its first step is shorter than Hairer's
+        assert int(hip["n_rej"][cases.STIFF]) > 0
+    assert len(set(hip["n_acc"][S].tolist())) > 1 and int(hip["n_rej"][S].sum()) > 0
+
+
 # ------------------------------------------------------------------------------------- 4. fine grid, growing tapes
 def test_matches_a_much_finer_rk4_solve_and_the_tapes_grow():
     """Property at a batch of several waves: agreement with a fixed-grid solve on a grid 8 times finer, in float64, within
@@ -287,13 +368,18 @@ class _Guarded:
         return bool((self.whole[:GUARD] == self.fill).all()) and bool((self.whole[GUARD + self.n:] == self.fill).all())
 
 
-@pytest.mark.parametrize("D,B,T,K", [(12, 70, 9, 1), (6, 3, 7, 2), (4, 65, 5, 1)])
-def test_nothing_is_written_outside_the_buffers_and_repeats_are_bit_identical(D, B, T, K):
+@pytest.mark.parametrize("D,B,T,K,grid", [(12, 70, 9, 1, None), (6, 3, 7, 2, None), (4, 65, 5, 1, None), (12, 70, 12, 3, "clustered")],
+                         ids=["12-70-9-1", "6-3-7-2", "4-65-5-1", "clustered-12-70-12-3"])
+def test_nothing_is_written_outside_the_buffers_and_repeats_are_bit_identical(D, B, T, K, grid):
     """Through the C ABI with buffers of our own: guard zones around h, the per-patient counters, the status word, the
     workspace and every gradient stay as they were, and a second forward + backward gives the same bits everywhere."""
     from hode import _dopri5_pp_lib as PL, _lib as L
     dev = _dev()
-    inp, f = cases.setup({"B": B, "T": T, "D": D, "K": K, "ablate": False, "hill": "two", "seed": 70 + D})
+    if grid is None:
+        inp, f = cases.setup({"B": B, "T": T, "D": D, "K": K, "ablate": False, "hill": "two", "seed": 70 + D})
+    else:  # several h rows per step, steps without one, three doses inside grid steps
+        inp, f = cases.setup(cases._grid_case(grid, D, B, K))
+        assert inp["t"].numel() == T
     y0, theta, w, b, t, dosage, times = _device_args(inp, f, dev)
     lib = PL.lib()
     M, steps = D - 4, 16 * T + 64
