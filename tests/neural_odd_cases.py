@@ -5,7 +5,9 @@ module: no tests here.
 Fixed grid: every odd size x three methods at N = 17 (one full 16-patient wave and one lane of the next), T = 6, on
 hode.synth's inputs with z0 * 30; one more case with perturb, one with a dose on a stage time (the midpoint of a grid
 step: t0 + dt / 2 is exact in fp32 and fp64 on the dyadic grid).  dopri5: D = 5 (fewest hidden tiles, ragged last one) and
-D = 15 (most) at N in {1, 17} with the replay checks, the other sizes once at N = 17."""
+D = 15 (most) at N in {1, 17} with the replay checks, the other sizes once at N = 17.  All of these are on synth's uniform
+0.125 grid from 0; two different step sizes in one call, a start at t[0] != 0 and, for dopri5, several output times inside
+one accepted step are tests/time_grids.py's neural_odd and neural_odd_dopri5 families (tests/test_hip_time_grids.py)."""
 import copy
 import functools
 

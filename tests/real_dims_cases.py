@@ -10,8 +10,10 @@ the edge shapes
     D  5, 7, 8, 9, 19      M = D - 4 = 1, 3 (a partial quad), 4 (exactly one quad), 5, 15
     H  1, 16, 17, 43, 64   the hidden-tile boundaries
     B  1, 15, 16, 17, 37   the wave boundary (16 patients per wave); more than one wave through the fold
-Time axis of every case: Ta = 12 action rows and the grid t = 5, 6, .., 11 (six steps), so that doses fall before and
-inside the window; perturb is True for midpoint / rk4 and False for euler, as in tests/test_hip_real.py."""
+Time axis of every case of this table: Ta = 12 action rows and the grid t = 5, 6, .., 11 (six steps), so that doses fall
+before and inside the window; perturb is True for midpoint / rk4 and False for euler, as in tests/test_hip_real.py.  That
+is a unit grid (dt = 1, every stage of a step inside one hour); the library's kernels run on non-uniform and offset grids,
+past the last action row and at negative times in tests/time_grids.py's real_dims family (tests/test_hip_time_grids.py)."""
 
 DIMS = tuple(range(5, 20))        # what real_solver_library gives the side library
 ACCEPTED = tuple(range(5, 21))    # what the library's entries accept

@@ -12,8 +12,11 @@ Not a cross product.  Every case runs forward + backward.  The table holds every
     N  1, 2, 7                 intervals
     S  1, 2, 3                 solver steps per interval (step_size 1, 1/2, 1/3 on a unit grid)
     C  0 (the library's choice), 1, 2, 3, N, N + 2: runs that end inside N and exactly on it
-Time axis of every case: Ta = 12 action rows and the grid t = 4, 5, .., 4 + N, so that doses fall before and inside the
-window; perturb is True for midpoint / rk4 and False for euler, as in tests/real_dims_cases.py."""
+Time axis of every case of this table: Ta = 12 action rows and the grid t = 4, 5, .., 4 + N, so that doses fall before and
+inside the window; perturb is True for midpoint / rk4 and False for euler, as in tests/real_dims_cases.py.  On that unit
+grid every row of the (N, S + 1) table is its neighbour shifted by 1 and all sub-steps are equal; intervals of different
+lengths, a clipped last sub-step and the starts 0.0, 2.5 and -1.0 are tests/time_grids.py's real_step family
+(tests/test_hip_time_grids.py)."""
 
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2}
 HTS = (1, 2, 3, 4)

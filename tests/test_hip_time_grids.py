@@ -5,6 +5,11 @@ fp32 / fp64 stage times on the same side of every dose time, inputs that tell a 
 oracle within half of every bound).  Every other GPU file feeds the kernels a uniform grid from 0 or an integer, where dt is
 one number and the step size or stage time of step n +- 1 gives the right answer.
 
+The side libraries that serve the ragged latent sizes are separately compiled instantiations and have families of their own:
+real_dims (libhode_real_dims.so), real_step (libhode_real_step.so: per-interval rows of the (N, S + 1) grid table, a clipped
+last sub-step, bit-identity with the chained kernels at S = 1 and across run lengths) and neural_odd / neural_odd_dopri5
+(libhode_neural_odd.so).  Each of their tests asserts which library served the call.
+
 Helpers, references and tolerances are those of tests/test_hip_kernel_variants.py: oracle.solvers.odeint on oracle.rhs in
 fp64 on the fp32 inputs, the fp64 tape replay for dopri5, tests/neural_real_eager.py; trajectory _traj_ok, gradients
 rel-L2 1e-4 (2e-4 for the real-data neural ODEs), grad_theta per component, h[0] == y0 bit for bit."""
@@ -140,6 +145,10 @@ def test_dopri5_time_grid(case, record_property):
 def test_neural_dopri5_time_grid(case, record_property):
     """ndp_* on the clustered and offset+ grids against oracle.solvers.odeint_dopri5_replay in fp64 along the run's own tape
     (test_neural_dopri5's bounds)."""
+    _neural_dopri5_on_grid(case, record_property)
+
+
+def _neural_dopri5_on_grid(case, record_property):
     from hode import adaptive
     from oracle.solvers import odeint_dopri5_replay
     from test_hip_neural import _neural_case, _neural_hip_dopri5
@@ -190,6 +199,150 @@ def test_real_time_grid(case, record_property):
         e = _rel(got[k], ref[k])
         record_property("err_" + k, e)
         assert e <= 1e-4, (k, e)
+
+
+# ---------------------------------------------------------------- real-data Roche at the ragged sizes (libhode_real_dims.so)
+@pytest.mark.parametrize("case", tg.family("real_dims"), ids=tg.case_id)
+def test_real_dims_time_grid(case, record_property):
+    """real_dims_kernel<HT, method, fwd / bwd> (the on-chip backward, the only one the library has) and its folds: step sizes
+    that differ within one call, stages of one step on both sides of an integer time, rows past the last action row and,
+    from -1.0, negative stage times; rk4 also without perturb (the last stage exactly on t1)."""
+    from hode import _real_dims_lib as RD
+    dev = _dev()
+    H, method = case["H"], case["method"]
+    assert RD.real_solver_library(case["D"]) is RD.side_library()
+    p, ref = tg.real_problem(case)
+    assert p["y0"].shape == (case["B"], case["D"]) and p["perturb"] == case["perturb"]
+    got = _real_gpu(p, H, method, dev)
+    assert torch.equal(got["h"][0].cpu(), p["y0"])
+    record_property("err_h", _err_h(got["h"], ref["h"]))
+    _traj_ok(got["h"], ref["h"])
+    for k in ("gy0", "gw", "gth"):
+        e = _rel(got[k], ref[k])
+        record_property("err_" + k, e)
+        assert e <= 1e-4, (k, e)
+
+
+# ------------------------------------------------------------------------------- one-step-ahead (libhode_real_step.so)
+STEP_GRADS = ("ginit", "gw", "gth")
+
+
+def _real_step_gpu(p, case, dev, C=None):
+    """hode.real_step.real_step_solve + autograd on the case's grid, with its step_size and run length (C overrides)."""
+    from hode.real_step import real_step_solve
+    wflat = p["wflat"].to(dev).requires_grad_(True)
+    theta = p["theta"].to(dev).requires_grad_(True)
+    init = p["init"].to(dev).requires_grad_(True)
+    h = real_step_solve(init, theta, wflat, p["t"].to(dev), p["a"][..., 0].to(dev), case["H"], method=case["method"],
+                        perturb=case["perturb"], step_size=p["step_size"], intervals_per_wave=case["C"] if C is None else C)
+    (h * p["cot"].to(dev)).sum().backward()
+    torch.cuda.synchronize()
+    return dict(h=h.detach(), ginit=init.grad, gw=wflat.grad, gth=theta.grad)
+
+
+def _real_step_ok(got, ref, record_property=None, keys=STEP_GRADS):
+    if record_property is not None:
+        record_property("err_h", _err_h(got["h"], ref["h"]))
+    _traj_ok(got["h"], ref["h"])
+    for k in keys:
+        assert torch.isfinite(got[k]).all(), k
+        e = _rel(got[k], ref[k]) if float(ref[k].abs().max()) > 0 else float(got[k].abs().max())
+        if record_property is not None:
+            record_property("err_" + k, e)
+        assert e <= 1e-4, (k, e)
+
+
+@pytest.mark.parametrize("case", tg.family("real_step"), ids=tg.case_id)
+def test_real_step_time_grid(case, record_property):
+    """real_step_dose_kernel, real_step_kernel<HT, method, fwd / bwd> and the folds against one fp64 oracle solve per interval:
+    intervals of different lengths (every row of the (N, S + 1) table is its own), on sub2 / sub3 a clipped last sub-step
+    of another length in every interval, from the starts 0.0, 2.5 and -1.0."""
+    from hode import _real_step_lib as RS
+    from hode.real_step import interval_grids
+    dev = _dev()
+    p, ref = tg.real_step_inputs(case), tg.real_step_ref(case)
+    assert interval_grids(p["t"], p["step_size"]).shape == (case["N"], case["S"] + 1)
+    got = _real_step_gpu(p, case, dev)
+    assert RS.LIBRARY.handle is not None  # real_step_solve has no other library to call: it is loaded by now
+    assert got["h"].shape == (case["N"] + 1, case["B"], case["D"]) and got["ginit"].shape == p["init"].shape
+    assert bool((got["h"][0] == 0).all())
+    _real_step_ok(got, ref, record_property)
+
+
+@pytest.mark.parametrize("case", [c for c in tg.family("real_step") if c["grid"] == "ragged"][:3], ids=tg.case_id)
+def test_real_step_matches_the_chained_kernels_on_intervals_that_differ(case):
+    """S = 1 on the ragged grid from each start: h[i + 1] and grad_init[i] are real_solve(init[i], t[i : i + 2]) bit for bit --
+    libhode_real_dims.so at D <= 19, libhode.so at 20 --, interval by interval
+    (test_hip_real_step.test_one_step_matches_the_chained_kernels_interval_by_interval where no two intervals are alike)."""
+    import hode
+    from hode import _real_dims_lib as RD
+    from hode.real import real_solve
+    dev = _dev()
+    assert case["S"] == 1
+    p = tg.real_step_inputs(case)
+    got = _real_step_gpu(p, case, dev)
+    t, act, cot = p["t"].to(dev), p["a"][..., 0].to(dev), p["cot"].to(dev)
+    assert RD.real_solver_library(case["D"]) is (hode.lib() if case["D"] == 20 else RD.side_library())
+    gw = torch.zeros_like(got["gw"])
+    for i in range(case["N"]):
+        y0 = p["init"][i].to(dev).requires_grad_(True)
+        wflat = p["wflat"].to(dev).requires_grad_(True)
+        hc = real_solve(y0, p["theta"].to(dev), wflat, t[i:i + 2], act, case["H"], method=case["method"], perturb=case["perturb"])
+        (hc[1] * cot[i + 1]).sum().backward()
+        same_h, same_g = torch.equal(hc[1].detach(), got["h"][i + 1]), torch.equal(y0.grad, got["ginit"][i])
+        assert same_h and same_g, (i, same_h, same_g)
+        gw += wflat.grad
+    assert _rel(got["gw"], gw) <= 1e-4
+
+
+@pytest.mark.parametrize("case", [next(c for c in tg.family("real_step") if c["grid"] == g and c["N"] == 7 and c["B"] == 37)
+                                  for g in ("sub2", "sub3")], ids=tg.case_id)
+def test_real_step_run_length_changes_no_state_on_sub_step_grids(case):
+    """h and grad_init do not depend on how the intervals are cut into runs (C = 0, 1, 2, 3, N, N + 2) where every interval
+    has a row and a clipped sub-step of its own; the folded gradients change in their summation order only and are held to
+    the fp64 bound for each C."""
+    dev = _dev()
+    p, ref = tg.real_step_inputs(case), tg.real_step_ref(case)
+    N = case["N"]
+    default = _real_step_gpu(p, case, dev, C=0)
+    for C in (0, 1, 2, 3, N, N + 2):
+        forced = _real_step_gpu(p, case, dev, C=C)
+        assert torch.equal(forced["h"], default["h"]) and torch.equal(forced["ginit"], default["ginit"]), C
+        _real_step_ok(forced, ref)
+
+
+# ------------------------------------------------------------------- NeuralODE at the odd sizes (libhode_neural_odd.so)
+def _served_by_the_odd_library(D):
+    from hode import _lib as L, _neural_odd_lib as NO
+    lib = NO.neural_solver_library(D)
+    assert isinstance(lib, NO._AsLibhode) and lib is not L.lib()
+
+
+@pytest.mark.parametrize("case", tg.family("neural_odd"), ids=tg.case_id)
+def test_neural_odd_time_grid(case, record_property):
+    """neural_mf_fwd_kernel<D, method> and neural_mf_bwd_kernel<D, method, true> at D = 5, 7, .., 15: two and more different
+    step sizes in one call, a grid across zero from -1.0, impulse doses on nodes and before t[0]."""
+    dev = _dev()
+    method, perturb = case["method"], case["perturb"]
+    _served_by_the_odd_library(case["D"])
+    p = tg.neural_inputs(case)
+    ref = tg.neural_solve_cpu(p, method, perturb)
+    got = _neural_gpu(p, method, perturb, dev)
+    assert torch.equal(got["h"][0].cpu(), p["y0"])
+    record_property("err_h", _err_h(got["h"], ref["h"]))
+    _traj_ok(got["h"], ref["h"])
+    for k in NEURAL_GRADS:
+        err = _rel(got[k], ref[k]) if float(ref[k].abs().max()) > 0 else float(got[k].abs().max())
+        record_property("err_" + k, err)
+        assert err <= 1e-4, (k, err)
+
+
+@pytest.mark.parametrize("case", tg.family("neural_odd_dopri5"), ids=tg.case_id)
+def test_neural_odd_dopri5_time_grid(case, record_property):
+    """ndp_*<D> at the odd sizes: the dense-output loop with several output times inside one accepted step and accepted steps
+    that cover none (clustered), and the whole solve from t[0] = 2.5 (offset+), against the fp64 replay of the run's own tape."""
+    _served_by_the_odd_library(case["D"])
+    _neural_dopri5_on_grid(case, record_property)
 
 
 # ------------------------------------------------------------------------------------------------------- neural real

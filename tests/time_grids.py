@@ -9,6 +9,10 @@ of calls (CASES) and their float64 problems.  A plain helper module, not a conft
 Every other GPU test feeds the kernels a uniform grid that starts at 0 or at an integer: there dt is one number, and a
 kernel that took the step size or a stage time of step n +- 1 instead of step n would still be right.
 
+The families real_dims, real_step, neural_odd and neural_odd_dopri5 (SIDE_CASES) put the ragged-size side libraries
+libhode_real_dims.so, libhode_real_step.so and libhode_neural_odd.so on the same grids; the one-step-ahead solve also gets
+sub2 and sub3, whose intervals take two / three solver steps with a clipped last one of another length in every interval.
+
 All nodes are multiples of 1/64 (1/256 on the clustered grid), so t[n], dt and dt / 2 are exact in fp32 and in fp64."""
 import copy
 import functools
@@ -219,8 +223,95 @@ def _real_cases():
     return out
 
 
-CASES = _roche_cases() + _neural_cases() + _dopri5_cases() + _real_cases()
-FIXED_FAMILIES = ("roche", "neural", "real", "neural_real")
+# ------------------------------------------------------------------------------------- the ragged-size side libraries
+# libhode_real_dims.so, libhode_real_step.so and libhode_neural_odd.so are separately compiled instantiations: the families
+# above say nothing about them.  The bindings route by latent size, so the same calls reach them.
+def _real_dims_cases():
+    """real_dims_kernel<HT, method, fwd / bwd>: every (HT, method) pair on the ragged and the offset+ grid, one case per method
+    on offset- (negative stage times); sizes from the edges tests/real_dims_cases.py names.  perturb alternates, so rk4 runs
+    without it too (the last stage exactly on t1).  The library serves the on-chip backward only (no operand-tape mode:
+    csrc/real_dims/hode_real_dims.hip refuses a NULL grad_w1)."""
+    out, i = [], 0
+    hs = {1: (1, 16), 2: (17, 17), 3: (43, 43), 4: (64, 64)}
+    ds, bs = (5, 7, 8, 9, 19), (1, 17, 37)
+
+    def add(ht, method, g):
+        nonlocal i
+        out.append(dict(family="real_dims", D=ds[i % 5], H=hs[ht][(i // 2) % 2], B=bs[i % 3], method=method,
+                        perturb=bool((i // 2 + i) % 2), grid=g, T=REAL_T))
+        i += 1
+
+    for ht in (1, 2, 3, 4):
+        for method in kv.METHODS:
+            add(ht, method, "ragged")
+            add(ht, method, "offset+")
+    for ht, method in ((2, "euler"), (3, "midpoint"), (4, "rk4")):
+        add(ht, method, "offset-")
+    return out
+
+
+# one-step-ahead: N intervals, each solved on its own row of the (N, S + 1) table of hode.real_step.interval_grids
+SUB_LENGTHS = {"sub2": (48, 64, 40, 56, 36, 64, 44),   # units of 1/64 with step_size 0.5: two sub-steps, the last one clipped
+               "sub3": (36, 48, 40, 44, 48, 34, 47)}   # with step_size 0.25: three sub-steps, the last one clipped
+SUB_STEP_SIZE = {"ragged": None, "sub2": 0.5, "sub3": 0.25}
+SUB_STEPS = {"ragged": 1, "sub2": 2, "sub3": 3}
+STEP_STARTS = (0.0, 2.5, -1.0)
+# action rows per (grid, start), so that over its three starts every grid has doses before the window and inside it and a
+# stage past the last row (the min(Ta, .) clamp).  ragged spans 1.05 hours: from 0.0 the dose of hour 1 falls inside it, from
+# 2.5 both doses lie before it and the stages from t = 3 on read past them.  sub2 / sub3 span 5.5 / 4.6 hours: from 0.0 and
+# 2.5 they hold doses and end past the last row.  The grids from -1.0 start with negative stage times (no dose yet).
+STEP_TA = {("ragged", 0.0): 1, ("ragged", 2.5): 2, ("ragged", -1.0): 2,
+           ("sub2", 0.0): 4, ("sub2", 2.5): 5, ("sub2", -1.0): 3,
+           ("sub3", 0.0): 3, ("sub3", 2.5): 5, ("sub3", -1.0): 2}
+
+
+def step_grid64(grid_name, start, N):
+    """The N + 1 nodes of a one-step-ahead grid as float64 (exact in fp32)."""
+    steps = RAGGED_STEPS if grid_name == "ragged" else SUB_LENGTHS[grid_name]
+    assert 1 <= N <= len(steps)
+    return start + np.concatenate([[0], np.cumsum(steps[:N])]) / 64.0
+
+
+def _real_step_cases():
+    """real_step_kernel<HT, method, fwd / bwd>: every (HT, method) pair; every (grid, start) twice; S 1, 2, 3; C 0, 1, 2, 3, N,
+    N + 2; N 2 and 7.  The first three ragged rows (starts 0.0, 2.5, -1.0; D 5, 20, 8) are the ones held bit for bit to the
+    chained kernels."""
+    rows = (  # D, H, B, N, C, method, grid, start
+        (5, 1, 17, 7, 0, "euler", "ragged", 0.0), (8, 16, 37, 7, 2, "midpoint", "sub2", 0.0), (19, 16, 1, 2, 1, "rk4", "sub3", 0.0),
+        (20, 17, 37, 7, 3, "euler", "sub3", 2.5), (20, 17, 17, 2, 4, "midpoint", "ragged", 2.5), (19, 17, 37, 7, 7, "rk4", "sub2", 2.5),
+        (8, 43, 1, 7, 9, "euler", "sub2", -1.0), (19, 43, 17, 7, 1, "midpoint", "sub3", -1.0), (8, 43, 37, 7, 0, "rk4", "ragged", -1.0),
+        (20, 64, 37, 2, 2, "euler", "sub3", 0.0), (5, 64, 17, 7, 3, "midpoint", "sub2", 2.5), (19, 49, 1, 7, 0, "rk4", "sub3", -1.0),
+        (19, 33, 37, 7, 7, "midpoint", "ragged", 0.0), (20, 1, 17, 7, 1, "rk4", "sub2", 0.0), (8, 16, 17, 7, 2, "rk4", "sub3", 2.5),
+        (19, 64, 17, 7, 3, "euler", "ragged", 2.5), (5, 17, 37, 2, 0, "midpoint", "sub2", -1.0), (20, 43, 1, 2, 4, "rk4", "ragged", -1.0))
+    return [dict(family="real_step", D=D, H=H, B=B, N=N, S=SUB_STEPS[g], C=C, method=m, perturb=bool(i % 2), grid=g, start=s)
+            for i, (D, H, B, N, C, m, g, s) in enumerate(rows)]
+
+
+NEURAL_ODD_DIMS = (5, 7, 9, 11, 13, 15)  # hode._neural_odd_lib.DIMS
+
+
+def _neural_odd_cases():
+    """neural_mf_fwd_kernel<D, method> and neural_mf_bwd_kernel<D, method, true> at the odd sizes: every D x method on the
+    ragged and the offset- grid (the library has the on-chip backward only)."""
+    out = []
+    for j, D in enumerate(NEURAL_ODD_DIMS):
+        for m, method in enumerate(kv.METHODS):
+            for k, g in enumerate(("ragged", "offset-")):
+                out.append(dict(family="neural_odd", D=D, method=method, B=(17, 37, 65)[(j + k) % 3], T=(8, 5, 2)[(j + m + k) % 3],
+                                perturb=bool((j + m + k) % 2), n_dose=(1, 3)[(j + m) % 2], grid=g))
+    return out
+
+
+def _neural_odd_dopri5_cases():
+    return [dict(family="neural_odd_dopri5", D=D, detach=detach, B=(17, 37, 33)[(j + detach) % 3],
+                 grid=("clustered", "offset+")[(j + detach) % 2], T=DOPRI5_T)
+            for j, D in enumerate(NEURAL_ODD_DIMS) for detach in (True, False)]
+
+
+OLD_CASES = _roche_cases() + _neural_cases() + _dopri5_cases() + _real_cases()
+SIDE_CASES = _real_dims_cases() + _real_step_cases() + _neural_odd_cases() + _neural_odd_dopri5_cases()
+CASES = OLD_CASES + SIDE_CASES
+FIXED_FAMILIES = ("roche", "neural", "real", "neural_real", "real_dims", "real_step", "neural_odd")
 
 
 def case_id(case):
@@ -247,6 +338,16 @@ def kernels(case):
         return kv.real_kernels(case["D"], case["H"], kv.METHODS[case["method"]], case["onchip"])
     if f == "neural_real":
         return kv.neural_real_kernels(case["kind"], case["D"], case["H"], kv.METHODS[case["method"]])
+    if f == "real_dims":
+        import real_dims_cases
+        return real_dims_cases.kernels(case)
+    if f == "real_step":
+        import real_step_cases
+        return real_step_cases.kernels(case)
+    if f == "neural_odd":
+        return kv.neural_fixed(case["D"], kv.METHODS[case["method"]], 0, True)
+    if f == "neural_odd_dopri5":
+        return kv.neural_dopri5_kernels(case["D"], case["T"] - 1, case["detach"])
     raise ValueError(f)
 
 
@@ -353,7 +454,7 @@ def real_problem(case):
     """test_hip_kernel_variants._real_problem (inputs and the fp64 oracle on oracle.rhs.RocheRealRHS) on the case's grid."""
     from test_hip_kernel_variants import _real_problem
     t = tuple(float(x) for x in grid64(case["grid"], case["T"]))
-    return _real_problem(case["D"], case["H"], case["method"], case["perturb"], Ta=REAL_TA[case["grid"]], t=t)
+    return _real_problem(case["D"], case["H"], case["method"], case["perturb"], B=case.get("B", 37), Ta=REAL_TA[case["grid"]], t=t)
 
 
 def real_solve_cpu(case, p, dtype=torch.float64, t=None):
@@ -411,3 +512,75 @@ def neural_real_solve_cpu(case, dtype=torch.float64, t=None):
         h, rows = neural_real_eager.solve(case["kind"], y, *ps, a.to(dtype), tt, case["method"], perturb=case["perturb"])
     (h * cot.to(dtype)).sum().backward()
     return dict(h=h.detach(), gy0=y.grad, gw1=ps[0].grad, gb1=ps[1].grad, gw2=ps[2].grad, gb2=ps[3].grad), rows
+
+
+# ------------------------------------------------------------------------------------------- one-step-ahead (real_step)
+@functools.lru_cache(maxsize=None)
+def _real_step_inputs(D, H, B, N, grid_name, start):
+    """fp32 inputs of a one-step-ahead problem as tests/test_hip_real_step.py draws them, on the named grid: the rhs module,
+    doses on half of the (hour, patient) cells (patient 0 has the first and the last row whatever the draw), a start state
+    per interval and the cotangent of h."""
+    from oracle.rhs import RocheRealRHS
+    from test_hip_kernel_variants import _real_flat
+    Ta = STEP_TA[(grid_name, start)]
+    gen = torch.Generator().manual_seed(1000 * D + 10 * H + B + 7 * N)
+    torch.manual_seed(D + 3 * H)
+    f = RocheRealRHS(D, H)
+    a = (torch.rand(Ta, B, 1, generator=gen) < 0.5).float() * torch.rand(Ta, B, 1, generator=gen) * 2
+    a[0, 0, 0], a[Ta - 1, 0, 0] = 0.7, 0.4
+    t = torch.tensor(step_grid64(grid_name, start, N), dtype=torch.float32)
+    init = torch.randn(N, B, D, generator=gen) * 0.3
+    cot = torch.randn(N + 1, B, D, generator=gen)
+    wflat = torch.cat([q.detach().reshape(-1) for q in _real_flat(f)])
+    theta = torch.stack([f.k_immunity, f.kel, f.kel2]).detach()
+    return dict(f=f, init=init, a=a, t=t, cot=cot, wflat=wflat, theta=theta, Ta=Ta, step_size=SUB_STEP_SIZE[grid_name])
+
+
+def real_step_inputs(case):
+    return _real_step_inputs(case["D"], case["H"], case["B"], case["N"], case["grid"], case["start"])
+
+
+def real_step_rows(case, t=None):
+    """The (N, S + 1) table the kernels walk: hode.real_step.interval_grids on the fp32 grid."""
+    from hode.real_step import interval_grids
+    t = real_step_inputs(case)["t"] if t is None else torch.tensor(np.asarray(t), dtype=torch.float32)
+    return interval_grids(t, SUB_STEP_SIZE[case["grid"]])
+
+
+def real_step_solve_cpu(case, p, dtype=torch.float64, t=None, rows=None):
+    """sum(h * cot) and its gradients with one oracle solve per interval in `dtype`, on the fp32 inputs: interval i from
+    init[i] over t[i : i + 2] with the grid's step_size (`t` replaces the grid, the start states stay in place).  With `rows`
+    (an (N, S + 1) table) interval i is stepped along rows[i] as it stands, increasing or not, with oracle.solvers' own step
+    functions: what a kernel that walked those numbers would compute."""
+    from oracle.solvers import _FIXED, _Rhs, odeint as oracle_odeint
+    from test_hip_kernel_variants import _real_flat
+    f = copy.deepcopy(p["f"]).to(dtype)
+    f.set_action_static(p["a"].to(dtype))
+    init = p["init"].detach().to(dtype).clone().requires_grad_(True)
+    method, perturb = case["method"], case["perturb"]
+    ends = []
+    for i in range(case["N"]):
+        if rows is None:
+            tt = (p["t"] if t is None else torch.tensor(np.asarray(t))).to(dtype)
+            opts = {"perturb": perturb} if p["step_size"] is None else {"perturb": perturb, "step_size": p["step_size"]}
+            ends.append(oracle_odeint(f, init[i], tt[i:i + 2], method=method, options=opts)[-1])
+        else:
+            rhs, y, row = _Rhs(f), init[i], rows[i].to(dtype)
+            for t0, t1 in zip(row[:-1], row[1:]):
+                y = y + _FIXED[method](rhs, t0, t1 - t0, t1, y, perturb)
+            ends.append(y)
+    h = torch.stack([torch.zeros_like(ends[0])] + ends)
+    (h * p["cot"].to(dtype)).sum().backward()
+    return dict(h=h.detach(), ginit=init.grad, gw=torch.cat([q.grad.reshape(-1) for q in _real_flat(f)]),
+                gth=torch.stack([f.k_immunity.grad, f.kel.grad, f.kel2.grad]))
+
+
+@functools.lru_cache(maxsize=None)
+def _real_step_ref(D, H, B, N, grid_name, start, method, perturb):
+    case = dict(N=N, method=method, perturb=perturb)
+    return real_step_solve_cpu(case, _real_step_inputs(D, H, B, N, grid_name, start))
+
+
+def real_step_ref(case):
+    """The fp64 oracle of the case, computed once and left unchanged."""
+    return _real_step_ref(case["D"], case["H"], case["B"], case["N"], case["grid"], case["start"], case["method"], case["perturb"])
