@@ -2,7 +2,8 @@
 """Build the gfx950 kernel libraries in-tree with hipcc: `python build_hip.py [-j N] [--force]`.
 
 LIBRARIES has one row per library: its file name in hode/, the directory of its sources, its C ABI header and its compile
-units.  build() compiles the units of all rows in one thread pool (a unit is recompiled when a file of its depfile, its flags
+units; MORE_LIBRARIES holds further rows of the same type, and library(name) looks a row up in both.  build() compiles the
+units of all rows in one thread pool (a unit is recompiled when a file of its depfile, its flags
 or this script changed), links each library whose objects are newer than it, and writes digest(<library>) next to it as
 <library>.so.digest; tests and hode/_loader.py compare that stamp with the tree.  The digest covers the header, every source
 of the row's directory, the units' sources and everything they include from inside the tree, the flags and the units."""
@@ -87,6 +88,13 @@ def _real_step_units():
         [("hode_real_step_ht%d" % n, os.path.join(d, "hode_real_step_ht.hip"), ["-DHODE_REAL_STEP_HT=%d" % n]) for n in REAL_STEP_HTS]
 
 
+def _dose_units():
+    d = os.path.join(CSRC, "dose")
+    # -Wno-unused-function: hode_rk_host.hpp is included for the grid shape and the partial fold; its argument helpers are not called here
+    return [("hode_dose", os.path.join(d, "hode_dose.hip"), ["-Wno-unused-function"])] + \
+        [("hode_dose_d%d" % n, os.path.join(d, "hode_dose_dim.hip"), ["-DHODE_DIM=%d" % n]) for n in DP_DIMS]
+
+
 def _dopri5_pp_units():
     d = os.path.join(CSRC, "dopri5_pp")
     # -Wno-unused-function: hode_rk_host.hpp is included for the partial fold; its Roche argument helpers are not called here
@@ -134,6 +142,22 @@ LIBRARIES = {lib.name: lib for lib in (
     _side("snf"),                             # the Sylvester-flow posterior with its Monte-Carlo KL (EncoderSylvesterLSTM)
     _multi("dopri5_pp", _dopri5_pp_units),    # dopri5 of the hybrid Roche rhs with per-patient step control, a unit per DP_DIMS
 )}
+#: libraries beside that table (its keys are pinned by tests/test_build_hip.py), built, linked and stamped with it
+MORE_LIBRARIES = {lib.name: lib for lib in (
+    _multi("dose", _dose_units),              # the fixed-grid adjoint of the hybrid Roche rhs with dose gradients, a unit per DP_DIMS
+)}
+
+
+def library(name):
+    """The row of `name`, from LIBRARIES or MORE_LIBRARIES."""
+    return LIBRARIES[name] if name in LIBRARIES else MORE_LIBRARIES[name]
+
+
+def all_libraries():
+    """Every row of both tables, in build order."""
+    return list(LIBRARIES.values()) + list(MORE_LIBRARIES.values())
+
+
 OUT = LIBRARIES["libhode.so"].out
 OBJ = LIBRARIES["libhode.so"].obj
 _INCLUDE = re.compile(rb'^\s*#include\s+"([^"]+)"', re.M)
@@ -143,7 +167,7 @@ def _digest_sources(lib):
     """{name relative to the repository root: contents} of what `lib` is built from: the ABI header, every source of
     `src_dir`, the units' sources, and whatever these include in quotes, transitively, each name resolved against the
     including file.  An #include under #if counts (a superset is safe); one that leaves the tree or names no file does not."""
-    lib = LIBRARIES[lib]
+    lib = library(lib)
     todo = [lib.src_dir + "/" + f for f in os.listdir(os.path.join(ROOT, lib.src_dir)) if f.endswith((".hpp", ".hip", ".h"))]
     todo += [lib.header] + [os.path.relpath(s, ROOT).replace(os.sep, "/") for _, s, _ in lib.units()]
     files = {}
@@ -172,7 +196,7 @@ def digest(lib):
     for f, text in sorted(_digest_sources(lib).items()):
         h.update(f.encode())
         h.update(text)
-    us = [(n, os.path.relpath(s, ROOT).replace(os.sep, "/"), e) for n, s, e in LIBRARIES[lib].units()]
+    us = [(n, os.path.relpath(s, ROOT).replace(os.sep, "/"), e) for n, s, e in library(lib).units()]
     h.update(repr((FLAGS, us)).encode())
     return h.hexdigest()
 
@@ -233,7 +257,7 @@ def link(out, objs):
 def build(jobs=7, force=False, verbose=True):
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
         futs = []
-        for lib in LIBRARIES.values():
+        for lib in all_libraries():
             os.makedirs(lib.obj, exist_ok=True)
             futs += [ex.submit(compile_one, n, s, e, force, lib.obj) for n, s, e in lib.units()]
         for f in futs:
@@ -242,7 +266,7 @@ def build(jobs=7, force=False, verbose=True):
                 print("  hipcc %-14s %.1fs" % (name, dt), flush=True)
             if verbose and err.strip():
                 print(err[-2000:], file=sys.stderr)
-    for lib in LIBRARIES.values():
+    for lib in all_libraries():
         objs = [os.path.join(lib.obj, n + ".o") for n, _, _ in lib.units()]
         if force or not os.path.exists(lib.out) or os.path.getmtime(lib.out) < max(os.path.getmtime(o) for o in objs):
             link(lib.out, objs)

@@ -402,6 +402,37 @@ class _RochePatientDopri5(torch.autograd.Function):
         return gy0, gth, gw, gb, None, None, None, None, None, None, None
 
 
+class _RocheDoseGrad(torch.autograd.Function):
+    """h = odeint(RocheODE, y0, t, method) on a fixed grid with a gradient for the dosage as well (``RocheODE.dose_grad``).
+    Forward: the existing lane-per-patient forward, ``hode.roche_solve(..., lanes_per_patient=1)``, so h is bit for bit what
+    that call returns.  Backward: ``hode.dose.dose_backward`` (libhode_dose.so).  Gradients for y0, theta, w, b and dosage;
+    none for t and dose_times (their .grad stays None)."""
+
+    @staticmethod
+    def forward(ctx, y0, theta, w, b, t, dosage, dose_times, method, ablate, perturb, check_finite, library):
+        f32c = hode.solver._f32c
+        thc, tc, dosc, dtc = f32c(theta), f32c(t), f32c(dosage), f32c(dose_times)
+        wc = f32c(w) if w is not None else None
+        bc = f32c(b) if b is not None else None
+        with torch.no_grad():  # detached inputs: the forward keeps nothing for a backward of its own
+            h = hode.roche_solve(f32c(y0), thc, wc, bc, tc, dosc, dtc, method=method, ablate=ablate, perturb=perturb,
+                                 lanes_per_patient=1, check_finite=check_finite, library=library)
+        ctx.save_for_backward(h, thc, wc if wc is not None else thc, bc if bc is not None else thc, tc, dosc, dtc)
+        ctx.meta = (method, bool(ablate), bool(perturb), w is not None)
+        return h
+
+    @staticmethod
+    def backward(ctx, grad_h):
+        from hode import dose
+        h, thc, wc, bc, tc, dosc, dtc = ctx.saved_tensors
+        method, ablate, perturb, has_w = ctx.meta
+        need_th = bool(ctx.needs_input_grad[1])
+        gy0, gth, gw, gb, gdos = dose.dose_backward(h, thc, wc if has_w else None, bc if has_w else None, tc, dosc, dtc,
+                                                    hode.solver._f32c(grad_h), method=method, ablate=ablate, perturb=perturb,
+                                                    need_theta=need_th)
+        return gy0, gth, gw, gb, None, gdos, None, None, None, None, None, None
+
+
 class RocheODE(nn.Module):
     """Expert PK/PD block + ``tanh(W y + b)`` learned block; ``forward(t, y)`` is the rhs (model.py:446-555)."""
 
@@ -435,6 +466,9 @@ class RocheODE(nn.Module):
         # dopri5 only: "batch" = torchdiffeq's controller (one error norm, one dt for the whole batch); "patient" = a
         # controller per patient (hode.patient_dopri5); options["step_control"] of hode.odeint overrides it for one call
         self.step_control = "batch"
+        # fixed-grid methods only: True lets a gradient reach the treatment -- set_action takes the dosage from an action
+        # that requires grad differentiably, and the solve's backward fills dosage.grad (hode.dose, libhode_dose.so)
+        self.dose_grad = False
 
     # -- dose schedule -------------------------------------------------------------------------------------
     def set_action(self, action):
@@ -446,20 +480,29 @@ class RocheODE(nn.Module):
         the GPU waits (bench.py ``full_training_step.host_enqueue_ms``).  Two sync-free routes: a batch source that knows
         its data (``hode.batches.DeviceFolds``) attaches the precomputed schedule to the action tensor
         (``action.hode_schedule = (dosage, dose_index)``), and a tensor OBJECT that was analysed before and has not been written to
-        since (same object, same version counter) reuses its result."""
+        since (same object, same version counter) reuses its result.
+
+        With ``dose_grad`` on and an action that requires grad, the dosage is always taken from the action by ``torch.max``
+        (as the reference does: the gradient goes to ONE entry of the action per patient, also among equal doses); the two
+        routes may still supply the dose indices."""
+        track = bool(getattr(self, "dose_grad", False)) and action.requires_grad
         sched = getattr(action, "hode_schedule", None)
         if sched is not None:
             self.dosage, idx = sched
+            if track:
+                self.dosage = torch.max(action[..., 0], dim=0)[0]
             self.times = idx * self.step_size
             return
         # identity, not address: the cache keeps the tensor alive, so its storage cannot be recycled for another batch
         cached = getattr(self, "_schedule_cache", None)
         if cached is not None and cached[0] is action and cached[1] == action._version:
             self.dosage, self.times = cached[2], cached[3] * self.step_size
+            if track:
+                self.dosage = torch.max(action[..., 0], dim=0)[0]
             return
         dosage, idx = dose_schedule_index(action)
         self.dosage, self.times = dosage, idx * self.step_size
-        self._schedule_cache = (action, action._version, dosage, idx)
+        self._schedule_cache = (action, action._version, dosage.detach() if track else dosage, idx)
 
     def dose_at_time(self, t):
         on = t >= self.times
@@ -494,6 +537,21 @@ class RocheODE(nn.Module):
         w = self.ml_net[0].weight if self.expanded else None
         b = self.ml_net[0].bias if self.expanded else None
         control = _step_control(self, options)  # the fixed-grid methods ignore it
+        if self.dose_grad:
+            from hode import dose
+            if method == "dopri5":
+                raise hode.HodeConfigError("hode: RocheODE.dose_grad serves the fixed-grid methods euler / midpoint / rk4; "
+                                           "method='dopri5' (step_control=%r) has no dose gradient" % (control,))
+            dose.check_domain(self.latent_dim)  # names the sizes held and libhode_dose.so; nothing is loaded or launched before
+            if self.dosage.requires_grad:
+                from hode import substep
+                perturb = bool(options.pop("perturb", False))
+                theta = self.theta_vector()
+                times = self.times.reshape(y0.shape[0], -1).to(torch.float32)
+                return substep.solve_with_step_size(
+                    lambda grid: _RocheDoseGrad.apply(y0, theta, w, b, grid, self.dosage, times, method, bool(self.ablate), perturb,
+                                                      bool(self.check_finite), None),
+                    t, options.pop("step_size", None))
         if method == "dopri5" and control == "patient":
             from hode import patient_dopri5
             patient_dopri5.check_domain(self.latent_dim)  # names the sizes held; nothing is loaded or launched before
