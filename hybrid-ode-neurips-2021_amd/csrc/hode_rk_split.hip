@@ -30,6 +30,10 @@
 //   * adjoint with the tape: the transposed product c_q = sum_j W[j][q] u_j (the learned block's share of the expert cotangent)
 //     runs on a wave of its own between the learned waves and the expert wave, which then lags two iterations; rings three
 //     deep (81.0 -> 79.4 us, bit-identical);
+//   * adjoint, learned waves: a stage VJP is six dependent links instead of nine -- at D = 12 W_LL^T u comes from the lane's
+//     own two rows (weights held rotated per quad lane, WllRot) and a two-round quad reduce-scatter of DPP adds instead of an
+//     all-gather of u and a four-deep packed chain, and for rk4 one fma separates two stage VJPs (sp_adjoint_step, ONE_LINK).
+//     335 -> 321 instructions per step, 64 -> 56 of them cross-lane; measured -1.0 .. -1.2 us of 77.6;
 //   * the time grid sits in LDS (dynamic shared memory, hence n_times <= 8192 for this layout);
 //   * time loops unrolled by two through a generic lambda so that ring parities are immediates; all ring reads of a step
 //     are issued up front and pinned with sched_barrier; per-step stores are unpredicated (lanes beyond the batch hold
@@ -46,6 +50,13 @@ namespace hode {
 
 #ifndef HODE_SPLIT_EXPERT_FIRST
 #define HODE_SPLIT_EXPERT_FIRST 1   // bias + expert columns of tanh(W y + b) ahead of the stage chain (MlRows::rhs_expert); 0: A/B
+#endif
+// The adjoint's stage VJP as six dependent links instead of nine, each part behind a switch of its own:
+#ifndef HODE_SPLIT_VJP_SCATTER
+#define HODE_SPLIT_VJP_SCATTER 1    // D = 12: W_LL^T u from the lane's own rows + a quad reduce-scatter (WllRot); 0: all-gather of u, A/B
+#endif
+#ifndef HODE_SPLIT_ADJ_ONE_LINK
+#define HODE_SPLIT_ADJ_ONE_LINK 1   // rk4, learned waves: one fma between two stage VJPs, the rest beside them (sp_adjoint_step); 0: A/B
 #endif
 constexpr int kSplitPatients = 48;  // per workgroup: wave 0 holds all 48 (one per lane), waves 1..3 hold 16 each
 
@@ -506,16 +517,43 @@ struct SplitBwdArgs {
 };
 
 // The cotangent algebra of one step of the scheme, shared by the expert wave (V = f2, two pairs) and the learned waves
-// (V = Own).  vjp(s, g) must return (df/dY)^T g at stage s.  lam is updated in place.
-template <int METHOD, class V, class F>
-HODE_DEV void sp_adjoint_step(V& lam, float dt, F&& vjp) {
+// (V = Own).  vjp(s, g) must return (df/dY)^T g at stage s; join(x) adds the step's own output cotangent (lv * grad_h) to
+// x.  lam is updated in place.
+// ONE_LINK (rk4, the learned waves): ONE fma between two stage VJPs -- the products with lam and with the earlier a_s do not
+// depend on the VJP in flight and are formed beside it, lam' = ((((lam + a3) + a2) + a1) + lv grad_h) + a0 is one add behind
+// a0, and the caller scales the last stage's cotangent by w1 = dt / 8 itself (folded into 1 - s^2, formed in the prelude), so
+// vjp(3, .) is handed lam as it stands: one link separates a0 from the next step's first u.  The expert wave keeps the
+// other form: it arrives at the barrier early either way, and with the one-link form its Disease cotangent came out one ulp
+// apart between the kernels with and without the theta wave, which must agree bit for bit.
+template <int METHOD, bool ONE_LINK, class V, class F, class J>
+HODE_DEV void sp_adjoint_step(V& lam, float dt, F&& vjp, J&& join) {
   constexpr float c13 = (float)(1.0 / 3.0);
   if constexpr (METHOD == HODE_METHOD_EULER) {
     lam += vjp(0, dt * lam);
+    lam = join(lam);
   } else if constexpr (METHOD == HODE_METHOD_MIDPOINT) {
     const V a1 = vjp(1, dt * lam);
     lam += a1;
     lam += vjp(0, (0.5f * dt) * a1);
+    lam = join(lam);
+  } else if constexpr (ONE_LINK) {
+    const float w1 = dt * 0.125f, w3 = dt * 0.375f, cdt = c13 * dt;
+    const V wl1 = w1 * lam, wl3 = w3 * lam;
+    const V a3 = vjp(3, lam);              // the caller's stage factor carries w1
+    const V g = vfma(dt, a3, wl3);
+    const V t2 = vfma(-dt, a3, wl3);       // these three beside vjp(2)
+    V t1 = vfma(dt, a3, wl1);
+    V s = lam;
+    s += a3;
+    const V a2 = vjp(2, g);
+    const V g2 = vfma(dt, a2, t2);
+    t1 = vfma(-cdt, a2, t1);               // beside vjp(1)
+    s += a2;
+    const V a1 = vjp(1, g2);
+    const V g1 = vfma(cdt, a1, t1);
+    s += a1;                               // beside vjp(0)
+    lam = join(s);
+    lam += vjp(0, g1);
   } else {
     const float w1 = dt * 0.125f, w3 = dt * 0.375f;
     const V a3 = vjp(3, w1 * lam);
@@ -533,6 +571,7 @@ HODE_DEV void sp_adjoint_step(V& lam, float dt, F&& vjp) {
     g1 = vfma(c13, dt * a1, g1);
     lam += a1;
     lam += vjp(0, g1);
+    lam = join(lam);
   }
 }
 
@@ -543,6 +582,56 @@ struct F4 {  // the expert wave's 4 components as two packed pairs
 };
 HODE_DEV F4 operator*(float s, const F4& v) { return F4{s * v.a, s * v.b}; }
 HODE_DEV F4 vfma(float s, const F4& x, const F4& y) { return F4{vfma(s, x.a, y.a), vfma(s, x.b, y.b)}; }
+
+// v = W_LL^T u on the learned waves at D = 12 (W_LL = W[:, 4:12]; quad lane q owns rows 2q, 2q+1 of W and with them
+// u = (u_2q, u_2q+1), and needs v_2q, v_2q+1).  Instead of gathering all eight u_i and summing over all rows for its own two
+// columns (8 DPP moves, a 4-deep packed fma chain, a join), a lane sums over its OWN two rows for all eight columns -- four
+// independent column pairs P[r], a packed mul + a packed fma each -- and the quad reduce-scatters the pairs with adds that
+// take their second operand through DPP.  The weights are stored rotated per lane, so that the register indices are the same
+// in every lane: w[r][h] holds columns 2 (r ^ q), 2 (r ^ q) + 1 of row 2q + h, hence P[r] of lane q is the partial sum for the
+// columns lane q ^ r owns.  Round 1 (partner q ^ 2): S[0] = P[0] + P[2]', S[1] = P[1] + P[3]'; round 2 (partner q ^ 1):
+// v = S[0] + S[1]'.  Every lane sums (lanes {q, q^2}) + (lanes {q^1, q^3}): the pairs {0, 2}, {1, 3} first, in every lane.
+constexpr int wll_rot_col(int q, int r, int c) { return 2 * (r ^ q) + c; }  // column of W_LL in half c of w[r][.] of lane q
+constexpr bool wll_rot_covers_once() {  // 4 lanes x 4 pairs x 2 rows x 2 halves = the 64 entries of W_LL, each exactly once
+  int seen[64] = {};
+  for (int q = 0; q < 4; ++q)
+    for (int r = 0; r < 4; ++r)
+      for (int h = 0; h < 2; ++h)
+        for (int c = 0; c < 2; ++c) ++seen[(2 * q + h) * 8 + wll_rot_col(q, r, c)];
+  for (int i = 0; i < 64; ++i)
+    if (seen[i] != 1) return false;
+  return true;
+}
+static_assert(wll_rot_covers_once(), "the rotated W_LL layout must hold every entry exactly once");
+
+struct WllRot {
+  f2 w[4][2];
+  HODE_DEV void load(const float* __restrict__ W, int q) {  // W: [8][12] row-major
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float* __restrict__ src = W + (2 * q + h) * 12 + 4 + wll_rot_col(q, r, 0);
+        w[r][h] = pair2(src[0], src[1]);
+      }
+  }
+  HODE_DEV f2 vjp(f2 u) const {
+    // quad_perm:[2,3,0,1] = 0x4E, quad_perm:[1,0,3,2] = 0xB1 (as quad_sum).  A VALU result needs two wait states before a
+    // DPP read: the pairs are formed and added in an order that leaves three instructions between every such pair.
+    f2 P[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) P[r] = w[r][0] * splat2(u.x);
+    P[3] = vfma(w[3][1], u.y, P[3]);
+    P[2] = vfma(w[2][1], u.y, P[2]);
+    P[1] = vfma(w[1][1], u.y, P[1]);
+    P[0] = vfma(w[0][1], u.y, P[0]);
+    const float s1x = P[1].x + dpp_f32<0x4E>(P[3].x);
+    const float s1y = P[1].y + dpp_f32<0x4E>(P[3].y);
+    const float s0x = P[0].x + dpp_f32<0x4E>(P[2].x);
+    const float s0y = P[0].y + dpp_f32<0x4E>(P[2].y);
+    return pair2(s0x + dpp_f32<0xB1>(s1x), s0y + dpp_f32<0xB1>(s1y));
+  }
+};
 
 // LDS of one backward workgroup, declared ONCE in the kernel and handed to the body instantiation that runs (a `__shared__`
 // array inside split_bwd_body exists once per instantiation: three of them -- HILL2 / K1 variants -- made 94 KB of 31).
@@ -558,12 +647,16 @@ struct SplitBwdShared {
   // their (masked) cotangent stays exactly zero without a per-stage multiply
   float cring[RD][4][kSplitPatients + 1][4];
   // Dose(t_s) [0..3] and dDose/dkel [4..7] of the 4 stages; written by the expert wave when it re-integrates, by the
-  // learned waves (stage q by quad lane q) when the stage states come from the tape
-  float dring[RD][kSplitPatients][8];
+  // learned waves (stage q by quad lane q) when the stage states come from the tape.  Element j of patient `slot` is at
+  // dose_ix(slot, j) (this ring, tdring) / u_ix(slot, j) (uring): the records as flat arrays with the index written out
+  // measured 1.9 us faster under the six-link stage VJP than the same layout declared [slot][8] / [slot][M]
+  float dring[RD][kSplitPatients * 8];
   float gring[RD][4][kSplitPatients + 1][4];    // THW: stage cotangents for the theta wave; row kSplitPatients: zeros
-  float tdring[RD][kSplitPatients][8];          // THW: the doses of the step the expert wave has just adjoined
-  float uring[CW ? RD : 1][4][CW ? kSplitPatients : 1][CW ? M : 1];   // CW: u = g (1 - s^2) of the learned rows, per stage
+  float tdring[RD][kSplitPatients * 8];         // THW: the doses of the step the expert wave has just adjoined
+  float uring[CW ? RD : 1][4][CW ? kSplitPatients * M : 1];   // CW: u = g (1 - s^2) of the learned rows, per stage
   float red[4][4][M * D + M];                   // epilogue: per-row partial sums of every gradient entry of a wave
+  static HODE_DEV int dose_ix(int slot, int j) { return slot * 8 + j; }
+  static HODE_DEV int u_ix(int slot, int j) { return slot * M + j; }
 };
 
 template <int D, int METHOD, bool ABLATE, bool HILL2, bool NEED_TH, bool K1, bool TAPE>
@@ -580,7 +673,8 @@ HODE_DEV void split_bwd_body(const SplitBwdArgs& a, SplitBwdShared<D, TAPE>& sh)
   // CW: see SplitBwdShared.  The learned waves' loop loses the M fmas + the LDS write of c_q per stage (-32 of ~350
   // instructions per step; they bound the adjoint) and gains one write of u.
   constexpr bool CW = TAPE;
-  constexpr int RD = SplitBwdShared<D, TAPE>::RD;
+  typedef SplitBwdShared<D, TAPE> Sh;
+  constexpr int RD = Sh::RD;
   constexpr int EL = CW ? 2 : 1;           // iterations the expert wave lags the learned waves
   constexpr int CWAVE = THW ? 5 : 4;       // wave index of the c-wave
   auto& yring = sh.yring; auto& cring = sh.cring; auto& dring = sh.dring; auto& gring = sh.gring;
@@ -674,8 +768,8 @@ HODE_DEV void split_bwd_body(const SplitBwdArgs& a, SplitBwdShared<D, TAPE>& sh)
           const DoseVal dv = ds.at(st.ts[s], th.kel);
           if (mine) {
             *reinterpret_cast<float4*>(&yring[par][s][slot][0]) = make_float4(Ya.x, Ya.y, Yb.x, Yb.y);
-            dring[par][slot][s] = dv.v;
-            dring[par][slot][4 + s] = dv.dk;
+            dring[par][Sh::dose_ix(slot, s)] = dv.v;
+            dring[par][Sh::dose_ix(slot, 4 + s)] = dv.dk;
           }
           if (s + 1 < NS) {
             const float Y[4] = {Ya.x, Ya.y, Yb.x, Yb.y};
@@ -711,13 +805,13 @@ HODE_DEV void split_bwd_body(const SplitBwdArgs& a, SplitBwdShared<D, TAPE>& sh)
         F4 cs[4];
         DoseVal dv[4];
         {
-          const float4 d0 = *reinterpret_cast<const float4*>(&dring[par][slot][0]);
-          const float4 d1 = *reinterpret_cast<const float4*>(&dring[par][slot][4]);
+          const float4 d0 = *reinterpret_cast<const float4*>(&dring[par][Sh::dose_ix(slot, 0)]);
+          const float4 d1 = *reinterpret_cast<const float4*>(&dring[par][Sh::dose_ix(slot, 4)]);
           dv[0].v = d0.x; dv[1].v = d0.y; dv[2].v = d0.z; dv[3].v = d0.w;
           dv[0].dk = d1.x; dv[1].dk = d1.y; dv[2].dk = d1.z; dv[3].dk = d1.w;
           if constexpr (THW) {
-            *reinterpret_cast<float4*>(&tdring[S][slot][0]) = d0;
-            *reinterpret_cast<float4*>(&tdring[S][slot][4]) = d1;
+            *reinterpret_cast<float4*>(&tdring[S][Sh::dose_ix(slot, 0)]) = d0;
+            *reinterpret_cast<float4*>(&tdring[S][Sh::dose_ix(slot, 4)]) = d1;
           }
         }
 #pragma unroll
@@ -729,7 +823,7 @@ HODE_DEV void split_bwd_body(const SplitBwdArgs& a, SplitBwdShared<D, TAPE>& sh)
           cs[s].a = pair2(cv.x, cv.y);
           cs[s].b = pair2(cv.z, cv.w);
         }
-        sp_adjoint_step<METHOD>(lam, dt, [&](int s, const F4& gs) {
+        sp_adjoint_step<METHOD, false>(lam, dt, [&](int s, const F4& gs) {
           const float g[4] = {gs.a.x, gs.a.y, gs.b.x, gs.b.y};
           float av[4];
           if constexpr (THW) {
@@ -740,10 +834,10 @@ HODE_DEV void split_bwd_body(const SplitBwdArgs& a, SplitBwdShared<D, TAPE>& sh)
           r.a += pair2(av[0], av[1]);
           r.b += pair2(av[2], av[3]);
           return r;
+        }, [&](const F4& x) {
+          const float4 g4 = *reinterpret_cast<const float4*>(a.grad_h + (size_t)m * row + lane_h);
+          return F4{vfma(lv, pair2(g4.x, g4.y), x.a), vfma(lv, pair2(g4.z, g4.w), x.b)};
         });
-        const float4 g4 = *reinterpret_cast<const float4*>(a.grad_h + (size_t)m * row + lane_h);
-        lam.a = vfma(lv, pair2(g4.x, g4.y), lam.a);
-        lam.b = vfma(lv, pair2(g4.z, g4.w), lam.b);
       }
       // ---- (a) stage states of step T-3-k for the learned waves' next iteration
       if (T - 3 - k >= 0) publish(T - 3 - k, par);
@@ -789,8 +883,8 @@ HODE_DEV void split_bwd_body(const SplitBwdArgs& a, SplitBwdShared<D, TAPE>& sh)
     // the theta terms of a step; stages in the order the expert wave's adjoint visits them (3, 2, 1, 0), so that every
     // accumulator sees its terms in the same order as when the expert wave accumulates them itself
     auto theta_step = [&](int gpar) {
-      const float4 d0 = *reinterpret_cast<const float4*>(&tdring[gpar][slot][0]);
-      const float4 d1 = *reinterpret_cast<const float4*>(&tdring[gpar][slot][4]);
+      const float4 d0 = *reinterpret_cast<const float4*>(&tdring[gpar][Sh::dose_ix(slot, 0)]);
+      const float4 d1 = *reinterpret_cast<const float4*>(&tdring[gpar][Sh::dose_ix(slot, 4)]);
       const float dvv[4] = {d0.x, d0.y, d0.z, d0.w}, dvk[4] = {d1.x, d1.y, d1.z, d1.w};
 #pragma unroll
       for (int si = 0; si < NS; ++si) {
@@ -844,7 +938,7 @@ HODE_DEV void split_bwd_body(const SplitBwdArgs& a, SplitBwdShared<D, TAPE>& sh)
         for (int s = 0; s < NS; ++s) {
 #pragma unroll
           for (int j4 = 0; j4 < M; j4 += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(&uring[cpar][s][slot][j4]);
+            const float4 v = *reinterpret_cast<const float4*>(&uring[cpar][s][Sh::u_ix(slot, j4)]);
             u[s][j4] = v.x; u[s][j4 + 1] = v.y; u[s][j4 + 2] = v.z; u[s][j4 + 3] = v.w;
           }
         }
@@ -889,14 +983,20 @@ HODE_DEV void split_bwd_body(const SplitBwdArgs& a, SplitBwdShared<D, TAPE>& sh)
     // unused with the c-wave).
     // MR == 2: wc[j] scalars, wtp[j] = (W[j][own0], W[j][own1]) (row-paired, the result is the Own pair);
     // MR == 1: wc[jp] = (W[2jp][q], W[2jp+1][q]), wtp[jp] = (W[2jp][own], W[2jp+1][own]) (paired over the rows j).
+    // SCATTER (MR == 2): the learned columns come from the lane's own rows instead (WllRot), wtp is unused.
+    constexpr bool SCATTER = MR == 2 && HODE_SPLIT_VJP_SCATTER;
+    // FOLD_W1: sp_adjoint_step's ONE_LINK form, with the weight of the first cotangent folded into the last stage's factor
+    constexpr bool FOLD_W1 = METHOD == HODE_METHOD_RK4_38 && HODE_SPLIT_ADJ_ONE_LINK;
     typename Ml::Elem wc[Ml::NU];
     f2 wtp[Ml::NU];
+    WllRot wrot;
     if constexpr (MR == 2) {
 #pragma unroll
       for (int j = 0; j < M; ++j) {
         wc[j] = a.w1[j * D + q];
         wtp[j] = pair2(a.w1[j * D + 4 + 2 * q], a.w1[j * D + 4 + 2 * q + 1]);
       }
+      if constexpr (SCATTER) wrot.load(a.w1, q);
     } else {
 #pragma unroll
       for (int jp = 0; jp < MP; ++jp) {
@@ -961,8 +1061,8 @@ HODE_DEV void split_bwd_body(const SplitBwdArgs& a, SplitBwdShared<D, TAPE>& sh)
         HODE_PSTAMP(k, 1)
         if constexpr (TAPE) {  // the expert wave adjoins this step EL iterations later: its doses, stage q by quad lane q
           const DoseVal dq = ds.at(sp_stage_time<METHOD>(t0, t1, a.perturb, q), th.kel);  // lanes q >= NS: unread
-          dring[par][slot][q] = dq.v;
-          if constexpr (NEED_TH) dring[par][slot][4 + q] = dq.dk;
+          dring[par][Sh::dose_ix(slot, q)] = dq.v;
+          if constexpr (NEED_TH) dring[par][Sh::dose_ix(slot, 4 + q)] = dq.dk;
         }
 #if HODE_SPLIT_EXPERT_FIRST
         typename Ml::Part pe[4];
@@ -983,15 +1083,29 @@ HODE_DEV void split_bwd_body(const SplitBwdArgs& a, SplitBwdShared<D, TAPE>& sh)
 #endif
         }
         // ---- adjoint of the stages
+        // FOLD_W1: the last stage's tanh' times the weight w1 = dt / 8 of the first cotangent, formed ahead of the chain
+        Own ds2w = vsplat<Own>(0.f);
+        if constexpr (FOLD_W1) ds2w = (dt * 0.125f) * vfma(-so[NS - 1], so[NS - 1], vsplat<Own>(1.0f));
         HODE_PSTAMP(k, 2)
-        sp_adjoint_step<METHOD>(lam, dt, [&](int s, Own gs) {
+        sp_adjoint_step<METHOD, FOLD_W1>(lam, dt, [&](int s, Own gs) {
           HODE_PSTAMP(k, 6 - s)
-          const Own u = gs * vfma(-so[s], so[s], vsplat<Own>(1.0f));
+          const Own u = gs * (FOLD_W1 && s == NS - 1 ? ds2w : vfma(-so[s], so[s], vsplat<Own>(1.0f)));
           db += u;
           Ml::outer_acc(dw, u, Y[s]);
           if constexpr (CW) {   // the c-wave forms c_q from it in the next iteration
-            if constexpr (MR == 2) *reinterpret_cast<float2*>(&uring[par][s][slot][2 * q]) = make_float2(u.x, u.y);
-            else uring[par][s][slot][q] = u;
+            if constexpr (MR == 2) *reinterpret_cast<float2*>(&uring[par][s][Sh::u_ix(slot, 2 * q)]) = make_float2(u.x, u.y);
+            else uring[par][s][Sh::u_ix(slot, q)] = u;
+          }
+          if constexpr (SCATTER) {
+            if constexpr (!CW) {   // c_q alone still takes the all-gather, in the order the c-wave sums (bit-identical to it)
+              typename Ml::Gath uf;
+              Ml::gather(u, uf.v);
+              float cq = 0.f;
+#pragma unroll
+              for (int j = 0; j < M; ++j) cq = __builtin_fmaf(wc[j], uf.v[j], cq);
+              cring[par][s][slot][q] = cq;
+            }
+            return wrot.vjp(u);
           }
           typename Ml::Gath uf;
           Ml::gather(u, uf.v);
@@ -1017,8 +1131,7 @@ HODE_DEV void split_bwd_body(const SplitBwdArgs& a, SplitBwdShared<D, TAPE>& sh)
             if constexpr (!CW) cring[par][s][slot][q] = hsum(c2);
             return hsum(a2);
           }
-        });
-        lam = vfma(lv, gh, lam);
+        }, [&](Own x) { return vfma(lv, gh, x); });
         HODE_PSTAMP(k, 7)
       }
       HODE_SSTAMP(k)
