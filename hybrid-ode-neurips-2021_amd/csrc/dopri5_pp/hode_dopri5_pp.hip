@@ -32,10 +32,7 @@ using hode_side::fail;
 
 size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 int n_waves(const hode_dopri5_pp_desc* d) { return (d->batch + hode::kPpLanes - 1) / hode::kPpLanes; }
-int n_partials(const hode_dopri5_pp_desc* d) {
-  const int M = d->latent_dim - 4;
-  return M * d->latent_dim + M + hode::kNTheta;
-}
+int n_partials(const hode_dopri5_pp_desc* d) { return hode::n_partials(d->latent_dim); }
 int max_attempts(const hode_dopri5_pp_desc* d) {
   if (d->max_attempts > 0) return d->max_attempts;
   const long long v = 8LL * d->max_steps + 1024;

@@ -11,7 +11,7 @@
 // Divergence.  Lanes of a wave take different numbers of attempts, so the attempt loop and the sweep run under a divergent
 // exec mask.  Nothing inside them crosses lanes: the LPP = 1 bodies of roche_rhs / roche_vjp / gather_rows / pick_own are
 // plain per-lane arithmetic (their DPP moves exist for LPP = 4 only), dp_stages and dp_step_factor likewise.  The
-// reductions (wave_sum in dp_store_grad_partials) and the status atomicOr come after the loops, where the wave has
+// reductions (wave_sum in store_grad_partials) and the status atomicOr come after the loops, where the wave has
 // reconverged.  Every loop is bounded by max_attempts / max_steps / T, none by data.
 //
 // All step sizes are constants in the backward, dt_0 included (the semantics of HODE_FLAG_DETACH_FIRST_STEP); the sigma /
@@ -52,15 +52,6 @@ struct PpLaunch {
 
 constexpr int kPpLanes = 64;  // patients per wave: lane per patient, full waves
 
-template <bool K1>
-HODE_DEV DoseSched<K1> pp_load_dose(const PpArgs& a, int p) {
-  DpArgs da{};
-  da.dosage = a.dosage;
-  da.dose_times = a.dose_times;
-  da.K = a.K;
-  return dp_load_dose<K1>(da, p);
-}
-
 // ------------------------------------------------------------------------------------------------------- forward
 template <int D, bool ABLATE, bool HILL2, bool K1>
 HODE_DEV void pp_fwd_body(const PpArgs& a) {
@@ -71,7 +62,7 @@ HODE_DEV void pp_fwd_body(const PpArgs& a) {
   const RocheTheta th = load_theta(a.theta, ABLATE);
   Ml ml;
   ml.load(a.w1, a.b1, 0);
-  const DoseSched<K1> ds = pp_load_dose<K1>(a, p);
+  const DoseSched<K1> ds = load_dose<K1>(a.dosage, a.dose_times, a.K, p);
   const size_t Bs = (size_t)a.B;
   const size_t row = Bs * D;
   const size_t poff = (size_t)p * D;
@@ -230,7 +221,7 @@ HODE_DEV void pp_bwd_body(const PpArgs& a) {
   MlColSlice<D, 1> mc;
   mc.load(a.w1, 0);
   const float ln_ec50 = log_f32(th.ec50);
-  const DoseSched<K1> ds = pp_load_dose<K1>(a, p);
+  const DoseSched<K1> ds = load_dose<K1>(a.dosage, a.dose_times, a.K, p);
   GradAcc<D, 1> acc;
   acc.zero();
   const size_t Bs = (size_t)a.B;
@@ -342,7 +333,7 @@ HODE_DEV void pp_bwd_body(const PpArgs& a) {
 
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   constexpr int P = M * D + M + kNTheta;
-  dp_store_grad_partials<D, 1, NEED_TH>(acc, a.grad_partials + (size_t)wave * P);
+  store_grad_partials<D, 1, NEED_TH>(acc, a.grad_partials + (size_t)wave * P);
 }
 
 template <int D, bool ABLATE, bool NEED_TH>

@@ -32,10 +32,7 @@ using hode_side::fail;
 
 size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 int n_waves(const hode_dose_desc* d) { return hode::n_waves_for(d->batch, 1); }
-int n_partials(const hode_dose_desc* d) {
-  const int M = d->latent_dim - 4;
-  return M * d->latent_dim + M + hode::kNTheta;
-}
+int n_partials(const hode_dose_desc* d) { return hode::n_partials(d->latent_dim); }
 size_t workspace_bytes(const hode_dose_desc* d) { return al256((size_t)n_waves(d) * n_partials(d) * sizeof(float)); }
 
 // what every entry checks first: the descriptor itself, the rhs kind, the method and the sizes

@@ -4,8 +4,6 @@
 #ifndef HODE_DIM
 #error "compile with -DHODE_DIM=<latent dim>"
 #endif
-#define HODE_CAT_(a, b) a##b
-#define HODE_CAT(a, b) HODE_CAT_(a, b)
 
 namespace hode {
 hipError_t HODE_CAT(dose_launch_d, HODE_DIM)(const DoseLaunch& L, const DoseArgs& a, hipStream_t s) {

@@ -91,16 +91,6 @@ __device__ constexpr float kDpMid[7] = {
 // row of tape_y that holds the state at the start of accepted step n
 HODE_DEV size_t dp_tape_row(const DpArgs& a, int n) { return (size_t)(a.ring ? (n & 1) : n); }
 
-template <bool K1>
-HODE_DEV DoseSched<K1> dp_load_dose(const DpArgs& a, int p) {
-  DoseSched<K1> ds;
-  ds.dosage = a.dosage[p];
-  ds.K = a.K;
-  ds.taus = a.dose_times + (size_t)p * a.K;
-  ds.tau0 = K1 ? ds.taus[0] : 0.f;
-  return ds;
-}
-
 // fold this launch's view of a per-wave partial array (fixed order => identical result in every lane of every wave).
 // The loads of a lane are issued together (16 in flight) before they are summed: a dependent load-add chain here costs
 // one L2 round trip per 64 partials on EVERY attempt.
@@ -156,7 +146,7 @@ HODE_DEV void dp_init1_body(const DpArgs& a) {
   const RocheTheta th = load_theta(a.theta, ABLATE);
   Ml ml;
   ml.load(a.w1, a.b1, lm.q);
-  const DoseSched<K1> ds = dp_load_dose<K1>(a, lm.p);
+  const DoseSched<K1> ds = load_dose<K1>(a.dosage, a.dose_times, a.K, lm.p);
   float y[D], f0[D], own[Ml::MR];
   load_vec<D>(a.y0 + (size_t)lm.p * D, y);
   roche_rhs<D, LPP, ABLATE, HILL2>(th, ml, ds.at(a.t[0], th.kel).v, y, f0, own);
@@ -189,7 +179,7 @@ HODE_DEV void dp_init2_body(const DpArgs& a) {
   const RocheTheta th = load_theta(a.theta, ABLATE);
   Ml ml;
   ml.load(a.w1, a.b1, lm.q);
-  const DoseSched<K1> ds = dp_load_dose<K1>(a, lm.p);
+  const DoseSched<K1> ds = load_dose<K1>(a.dosage, a.dose_times, a.K, lm.p);
   const float cnt = (float)a.B * (float)D;
   const float d0 = __builtin_sqrtf(fold_waves(a.partials, a.n_waves, 2, 0) / cnt);
   const float d1 = __builtin_sqrtf(fold_waves(a.partials, a.n_waves, 2, 1) / cnt);
@@ -398,7 +388,7 @@ HODE_DEV void dp_attempt_body(const DpArgs& a) {
   const RocheTheta th = load_theta(a.theta, ABLATE);
   Ml ml;
   ml.load(a.w1, a.b1, lm.q);
-  const DoseSched<K1> ds = dp_load_dose<K1>(a, lm.p);
+  const DoseSched<K1> ds = load_dose<K1>(a.dosage, a.dose_times, a.K, lm.p);
   const float t0f = (float)c.t0, dtf = (float)c.dt, t1f = (float)(c.t0 + c.dt);
   float k[7][D], Y[7][D], s[7][MR];
   DoseVal dv[7];
@@ -530,7 +520,7 @@ HODE_DEV void dp_attempt_body_own(const DpArgs& a) {
   const RocheTheta th = load_theta(a.theta, ABLATE);
   MlSlice<D, 4> ml;
   ml.load(a.w1, a.b1, q);
-  const DoseSched<K1> ds = dp_load_dose<K1>(a, lm.p);
+  const DoseSched<K1> ds = load_dose<K1>(a.dosage, a.dose_times, a.K, lm.p);
   const DpCtrl cin = a.ctrl[par];
   __builtin_amdgcn_sched_barrier(0);
   HODE_STAMP(1)   // level-1 loads back (the stamp waits for everything outstanding)
@@ -752,7 +742,7 @@ HODE_DEV void dp_persist_body_own(const DpArgs& a) {
   const RocheTheta th = load_theta(a.theta, ABLATE);
   MlSlice<D, 4> ml;
   ml.load(a.w1, a.b1, q);
-  const DoseSched<K1> ds = dp_load_dose<K1>(a, lm.p);
+  const DoseSched<K1> ds = load_dose<K1>(a.dosage, a.dose_times, a.K, lm.p);
   DpCtrl c = a.ctrl[0];
   if (c.done) return;
   float y[NO], f0[NO];
@@ -923,30 +913,6 @@ __global__ __launch_bounds__(PHASE == 2 ? 256 : 64) void dp_fwd_kernel(DpArgs a)
 //                              + (sum_j Q0_j G_j . f0 + sum_j Q1_j G_j . f1)/dt
 // (formulas checked against autograd in fp64; the replay oracle of tests/test_hip_dopri5.py pins the sum).  The kernels
 // dp_initbwd_* below push sigma through dt_0 = min(100 h0, h1) into grad_y0 and the parameter gradients.
-template <int D, int LPP, bool NEED_TH>
-HODE_DEV void dp_store_grad_partials(const GradAcc<D, LPP>& acc, float* __restrict__ out) {
-  constexpr int M = D - 4;
-  constexpr int MR = MlSlice<D, LPP>::MR;
-  const int lane = threadIdx.x & 63;
-  if constexpr (M > 0) {
-#pragma unroll
-    for (int r = 0; r < MR; ++r) {
-#pragma unroll
-      for (int i = 0; i < D; ++i) {
-        const float v = wave_sum_patients<LPP>(acc.dw[r][i]);
-        if (lane < LPP) out[(lane * MR + r) * D + i] = v;
-      }
-      const float vb = wave_sum_patients<LPP>(acc.db[r]);
-      if (lane < LPP) out[M * D + lane * MR + r] = vb;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < kNTheta; ++i) {
-    const float v = wave_sum_patients<LPP>(NEED_TH ? acc.dth[i] : 0.f);
-    if (lane == 0) out[M * D + M + i] = v;
-  }
-}
-
 template <int D, int LPP, bool ABLATE, bool HILL2, bool NEED_TH, bool K1>
 HODE_DEV void dp_bwd_body(const DpArgs& a) {
   using Ml = MlSlice<D, LPP>;
@@ -959,7 +925,7 @@ HODE_DEV void dp_bwd_body(const DpArgs& a) {
   MlColSlice<D, LPP> mc;
   mc.load(a.w1, lm.q);
   const float ln_ec50 = log_f32(th.ec50);
-  const DoseSched<K1> ds = dp_load_dose<K1>(a, lm.p);
+  const DoseSched<K1> ds = load_dose<K1>(a.dosage, a.dose_times, a.K, lm.p);
   GradAcc<D, LPP> acc;
   acc.zero();
   const size_t row = (size_t)a.B * D;
@@ -1118,7 +1084,7 @@ HODE_DEV void dp_bwd_body(const DpArgs& a) {
 
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   constexpr int P = M * D + M + kNTheta;
-  dp_store_grad_partials<D, LPP, NEED_TH>(acc, a.grad_partials + (size_t)wave * P);
+  store_grad_partials<D, LPP, NEED_TH>(acc, a.grad_partials + (size_t)wave * P);
 }
 
 // ------------------------------------------------------------------------------------------ backward, owner layout
@@ -1229,7 +1195,7 @@ HODE_DEV void dp_bwd_body_own(const DpArgs& a) {
     for (int r = 0; r < MR; ++r) wcol[j][1 + r] = a.w1[j * D + 4 + q * MR + r];
   }
   const float ln_ec50 = log_f32(th.ec50);
-  const DoseSched<K1> ds = dp_load_dose<K1>(a, lm.p);
+  const DoseSched<K1> ds = load_dose<K1>(a.dosage, a.dose_times, a.K, lm.p);
   GradAcc<D, 4> acc;
   acc.zero();
   const size_t row = (size_t)a.B * D;
@@ -1387,7 +1353,7 @@ HODE_DEV void dp_bwd_body_own(const DpArgs& a) {
 
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   constexpr int P = M * D + M + kNTheta;
-  dp_store_grad_partials<D, 4, NEED_TH>(acc, a.grad_partials + (size_t)wave * P);
+  store_grad_partials<D, 4, NEED_TH>(acc, a.grad_partials + (size_t)wave * P);
 }
 
 template <int D, int LPP, bool ABLATE, bool NEED_TH>
@@ -1443,7 +1409,7 @@ HODE_DEV void dp_initbwd_body(const DpArgs& a) {
   MlColSlice<D, LPP> mc;
   mc.load(a.w1, lm.q);
   const float ln_ec50 = log_f32(th.ec50);
-  const DoseSched<K1> ds = dp_load_dose<K1>(a, lm.p);
+  const DoseSched<K1> ds = load_dose<K1>(a.dosage, a.dose_times, a.K, lm.p);
   GradAcc<D, LPP> acc;
   acc.zero();
   const float live = lm.live ? 1.0f : 0.0f;
@@ -1526,7 +1492,7 @@ HODE_DEV void dp_initbwd_body(const DpArgs& a) {
 #pragma unroll
     for (int c = 0; c < D; ++c) gy[c] += yb[c] + a0[c];
     store_vec<D, LPP>(a.grad_y0 + (size_t)lm.p * D, gy, lm.q, lm.live);
-    dp_store_grad_partials<D, LPP, NEED_TH>(acc, gout);
+    store_grad_partials<D, LPP, NEED_TH>(acc, gout);
     if (wave == 0 && lane == 0) a.init->sigma = sigma;
   }
 }

@@ -4,6 +4,10 @@
 
 #include "../../include/hode.h"
 
+// pastes the value of a -D macro onto a name: the per-size entry of a *_dim.hip / *_tpw.hip unit
+#define HODE_CAT_(a, b) a##b
+#define HODE_CAT(a, b) HODE_CAT_(a, b)
+
 namespace hode {
 
 // records a thread-local message (returned by the library's *_last_error_string) and returns `code`; defined, with hip_fail
@@ -94,6 +98,7 @@ int hip_fail(hipError_t e, const char* what);
 int patients_per_wave(int B, int lpp);
 int n_waves_for(int B, int lpp);
 int choose_lpp(const hode_solve_desc* d);
+int n_partials(int latent_dim);  // floats of one partial row [w1 | b1 | theta]
 int n_partials(const hode_solve_desc* d);
 // out += fixed-order sum over waves of partials[w][0..P): [w1 | b1 | theta]
 int launch_fold_partials(const float* partials, int n_waves, int P, int n_w, int n_b, float* gw, float* gb, float* gth,

@@ -9,8 +9,6 @@
 #error "compile with -DHODE_LSTM_TPW=<unit tiles per wave of the backward>"
 #endif
 
-#define HODE_CAT_(a, b) a##b
-#define HODE_CAT(a, b) HODE_CAT_(a, b)
 
 #ifdef HODE_LSTM_SEQ_UNIT
 #define HODE_LSTM_FWD_KERNEL hode::lstm_seq_fwd_kernel

@@ -6,8 +6,6 @@
 #error "compile with -DHODE_DIM=<latent dim>"
 #endif
 
-#define HODE_CAT_(a, b) a##b
-#define HODE_CAT(a, b) HODE_CAT_(a, b)
 
 namespace hode {
 int HODE_CAT(rk_dispatch_d, HODE_DIM)(const RkLaunch& L, const RkArgs& a, hipStream_t s) {

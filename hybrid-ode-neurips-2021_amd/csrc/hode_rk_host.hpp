@@ -60,10 +60,11 @@ int choose_lpp(const hode_solve_desc* d) {
   return d->batch >= 131072 ? 1 : 4;
 }
 
-int n_partials(const hode_solve_desc* d) {
-  const int M = d->latent_dim - 4;
-  return M * d->latent_dim + M + kNTheta;
+int n_partials(int latent_dim) {
+  const int M = latent_dim - 4;
+  return M * latent_dim + M + kNTheta;
 }
+int n_partials(const hode_solve_desc* d) { return n_partials(d->latent_dim); }
 
 
 int launch_fold_partials(const float* partials, int n_waves, int P, int n_w, int n_b, float* gw, float* gb, float* gth,

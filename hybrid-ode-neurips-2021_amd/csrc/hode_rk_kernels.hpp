@@ -26,16 +26,6 @@ namespace hode {
 constexpr float kOneThird = (float)(1.0 / 3.0);
 constexpr float kTwoThirds = (float)(2.0 / 3.0);
 
-template <bool K1>
-HODE_DEV DoseSched<K1> load_dose(const RkArgs& a, int p) {
-  DoseSched<K1> ds;
-  ds.dosage = a.dosage[p];
-  ds.K = a.K;
-  ds.taus = a.dose_times + (size_t)p * a.K;
-  ds.tau0 = K1 ? ds.taus[0] : 0.f;
-  return ds;
-}
-
 // stage times of one step, rounded exactly like the fp32 tensor ops of the reference solver
 struct StageTimes {
   float t0, t1, dt, ta, tb, t_first, t_last;
@@ -86,7 +76,7 @@ HODE_DEV void rk_fwd_body(const RkArgs& a) {
   const RocheTheta th = load_theta(a.theta, ABLATE);
   Ml ml;
   ml.load(a.w1, a.b1, lm.q);
-  const DoseSched<K1> ds = load_dose<K1>(a, lm.p);
+  const DoseSched<K1> ds = load_dose<K1>(a.dosage, a.dose_times, a.K, lm.p);
 
   float y[D];
   load_vec<D>(a.y0 + (size_t)lm.p * D, y);
@@ -159,8 +149,21 @@ __global__ __launch_bounds__(64) void rk_fwd_kernel(RkArgs a) {
 template <int D, int LPP>
 constexpr int n_partials() { return (D - 4) * D + (D - 4) + kNTheta; }
 
-template <int D, int LPP, int METHOD, bool ABLATE, bool HILL2, bool NEED_TH, bool K1>
-HODE_DEV void rk_bwd_body(const RkArgs& a) {
+// The sweep's hook for the gradient of the dosage (dose/hode_dose_kernels.hpp).  A hook with kGrad set forms the dose of
+// every stage itself -- at(ds, ts, kel), a DoseVal that carries what its tap needs -- is handed the cotangent of every stage
+// VJP -- tap(stage dose, g[3], kel) -- and ends the sweep: finish(a, lm, lam).  This one does nothing.
+struct NoDoseGrad {
+  static constexpr bool kGrad = false;
+};
+
+template <class DOSE, bool K1>
+HODE_DEV auto stage_dose(const DOSE& dose, const DoseSched<K1>& ds, float ts, float kel) {
+  if constexpr (DOSE::kGrad) return dose.at(ds, ts, kel);
+  else return ds.at(ts, kel);
+}
+
+template <int D, int LPP, int METHOD, bool ABLATE, bool HILL2, bool NEED_TH, bool K1, class DOSE = NoDoseGrad>
+HODE_DEV void rk_bwd_body(const RkArgs& a, DOSE dose = {}) {
   using Ml = MlSlice<D, LPP>;
   constexpr int MR = Ml::MR;
   constexpr int M = D - 4;
@@ -171,7 +174,7 @@ HODE_DEV void rk_bwd_body(const RkArgs& a) {
   MlColSlice<D, LPP> mc;
   mc.load(a.w1, lm.q);
   const float ln_ec50 = log_f32(th.ec50);
-  const DoseSched<K1> ds = load_dose<K1>(a, lm.p);
+  const DoseSched<K1> ds = load_dose<K1>(a.dosage, a.dose_times, a.K, lm.p);
   GradAcc<D, LPP> acc;
   acc.zero();
 
@@ -202,12 +205,13 @@ HODE_DEV void rk_bwd_body(const RkArgs& a) {
     const StageTimes st(a.t, n, a.perturb, METHOD);
     const float dt = st.dt;
     float k1[D], s1[MR], a_[D], g[D];
-    const DoseVal dose1 = ds.at(st.t_first, th.kel);
+    const auto dose1 = stage_dose(dose, ds, st.t_first, th.kel);
     roche_rhs<D, LPP, ABLATE, HILL2>(th, ml, dose1.v, y, k1, s1);
     if constexpr (METHOD == HODE_METHOD_EULER) {
 #pragma unroll
       for (int i = 0; i < D; ++i) g[i] = dt * lam[i];
       roche_vjp<D, LPP, ABLATE, HILL2, NEED_TH>(th, ml, mc, ln_ec50, dose1, y, s1, g, lm.q, a_, acc);
+      if constexpr (DOSE::kGrad) dose.tap(dose1, g[3], th.kel);
 #pragma unroll
       for (int i = 0; i < D; ++i) lam[i] += a_[i];
     } else if constexpr (METHOD == HODE_METHOD_MIDPOINT) {
@@ -215,32 +219,34 @@ HODE_DEV void rk_bwd_body(const RkArgs& a) {
       const float half = 0.5f * dt;
 #pragma unroll
       for (int i = 0; i < D; ++i) Y2[i] = __builtin_fmaf(k1[i], half, y[i]);
-      const DoseVal dose2 = ds.at(st.ta, th.kel);
+      const auto dose2 = stage_dose(dose, ds, st.ta, th.kel);
       roche_rhs<D, LPP, ABLATE, HILL2>(th, ml, dose2.v, Y2, k2, s2);
 #pragma unroll
       for (int i = 0; i < D; ++i) g[i] = dt * lam[i];
       roche_vjp<D, LPP, ABLATE, HILL2, NEED_TH>(th, ml, mc, ln_ec50, dose2, Y2, s2, g, lm.q, a_, acc);
+      if constexpr (DOSE::kGrad) dose.tap(dose2, g[3], th.kel);
 #pragma unroll
       for (int i = 0; i < D; ++i) {
         lam[i] += a_[i];
         g[i] = half * a_[i];
       }
       roche_vjp<D, LPP, ABLATE, HILL2, NEED_TH>(th, ml, mc, ln_ec50, dose1, y, s1, g, lm.q, a_, acc);
+      if constexpr (DOSE::kGrad) dose.tap(dose1, g[3], th.kel);
 #pragma unroll
       for (int i = 0; i < D; ++i) lam[i] += a_[i];
     } else {
       float Y2[D], Y3[D], Y4[D], k2[D], k3[D], k4[D], s2[MR], s3[MR], s4[MR];
 #pragma unroll
       for (int i = 0; i < D; ++i) Y2[i] = __builtin_fmaf(dt * k1[i], kOneThird, y[i]);
-      const DoseVal dose2 = ds.at(st.ta, th.kel);
+      const auto dose2 = stage_dose(dose, ds, st.ta, th.kel);
       roche_rhs<D, LPP, ABLATE, HILL2>(th, ml, dose2.v, Y2, k2, s2);
 #pragma unroll
       for (int i = 0; i < D; ++i) Y3[i] = __builtin_fmaf(dt, __builtin_fmaf(-k1[i], kOneThird, k2[i]), y[i]);
-      const DoseVal dose3 = ds.at(st.tb, th.kel);
+      const auto dose3 = stage_dose(dose, ds, st.tb, th.kel);
       roche_rhs<D, LPP, ABLATE, HILL2>(th, ml, dose3.v, Y3, k3, s3);
 #pragma unroll
       for (int i = 0; i < D; ++i) Y4[i] = __builtin_fmaf(dt, (k1[i] - k2[i]) + k3[i], y[i]);
-      const DoseVal dose4 = ds.at(st.t_last, th.kel);
+      const auto dose4 = stage_dose(dose, ds, st.t_last, th.kel);
       roche_rhs<D, LPP, ABLATE, HILL2>(th, ml, dose4.v, Y4, k4, s4);  // only s4 is needed (k4 is dead code)
 
       const float w1 = dt * 0.125f, w3 = dt * 0.375f;
@@ -249,6 +255,7 @@ HODE_DEV void rk_bwd_body(const RkArgs& a) {
 #pragma unroll
       for (int i = 0; i < D; ++i) g[i] = w1 * lam[i];
       roche_vjp<D, LPP, ABLATE, HILL2, NEED_TH>(th, ml, mc, ln_ec50, dose4, Y4, s4, g, lm.q, a_, acc);
+      if constexpr (DOSE::kGrad) dose.tap(dose4, g[3], th.kel);
 #pragma unroll
       for (int i = 0; i < D; ++i) {
         const float da = dt * a_[i];
@@ -259,6 +266,7 @@ HODE_DEV void rk_bwd_body(const RkArgs& a) {
       }
       // stage 3
       roche_vjp<D, LPP, ABLATE, HILL2, NEED_TH>(th, ml, mc, ln_ec50, dose3, Y3, s3, g, lm.q, a_, acc);
+      if constexpr (DOSE::kGrad) dose.tap(dose3, g[3], th.kel);
 #pragma unroll
       for (int i = 0; i < D; ++i) {
         const float da = dt * a_[i];
@@ -268,6 +276,7 @@ HODE_DEV void rk_bwd_body(const RkArgs& a) {
       }
       // stage 2
       roche_vjp<D, LPP, ABLATE, HILL2, NEED_TH>(th, ml, mc, ln_ec50, dose2, Y2, s2, g2, lm.q, a_, acc);
+      if constexpr (DOSE::kGrad) dose.tap(dose2, g2[3], th.kel);
 #pragma unroll
       for (int i = 0; i < D; ++i) {
         g1[i] = __builtin_fmaf(kOneThird, dt * a_[i], g1[i]);
@@ -275,6 +284,7 @@ HODE_DEV void rk_bwd_body(const RkArgs& a) {
       }
       // stage 1
       roche_vjp<D, LPP, ABLATE, HILL2, NEED_TH>(th, ml, mc, ln_ec50, dose1, y, s1, g1, lm.q, a_, acc);
+      if constexpr (DOSE::kGrad) dose.tap(dose1, g1[3], th.kel);
 #pragma unroll
       for (int i = 0; i < D; ++i) lam[i] += a_[i];
     }
@@ -292,8 +302,11 @@ HODE_DEV void rk_bwd_body(const RkArgs& a) {
   if (a.T == 1) { /* lam already = grad_h[0] */ }
   if constexpr (kDwordRows<D, LPP>) store_dwords<D>(a.grad_y0 + (size_t)lm.p * D, lam, lm.q, lm.live);
   else store_vec<D, LPP>(a.grad_y0 + (size_t)lm.p * D, lam, lm.q, lm.live);
+  if constexpr (DOSE::kGrad) dose.finish(a, lm, lam);
 
-  // ---- fold the per-lane parameter gradients over the patients of this wave, one partial row per wave
+  // ---- fold the per-lane parameter gradients over the patients of this wave, one partial row per wave.  These are the
+  // lines of store_grad_partials (hode_roche.hpp), kept in place: behind a call the same lines are optimised on their own
+  // first, and the register allocation of the whole sweep moves (profiles/lane_sweep_device_code_diff.txt)
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   float* out = a.partials + (size_t)wave * n_partials<D, LPP>();

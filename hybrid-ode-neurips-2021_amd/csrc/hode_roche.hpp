@@ -13,6 +13,7 @@
 // at the 10k-patient shape; with LPP = 1 a wave covers 64 patients and the total instruction count is lowest.
 #pragma once
 #include "hode_common.hpp"
+#include "hode_lanes.hpp"
 
 namespace hode {
 
@@ -150,6 +151,17 @@ struct DoseSched {
   }
 };
 
+// the dose schedule of patient p out of the kernel's arguments (dose_times is [B][K])
+template <bool K1>
+HODE_DEV DoseSched<K1> load_dose(const float* dosage, const float* dose_times, int K, int p) {
+  DoseSched<K1> ds;
+  ds.dosage = dosage[p];
+  ds.K = K;
+  ds.taus = dose_times + (size_t)p * K;
+  ds.tau0 = K1 ? ds.taus[0] : 0.f;
+  return ds;
+}
+
 // x ** p with torch.pow semantics (negative base: finite for integer p, NaN otherwise); p == 2 is the shipped value
 template <bool HILL2>
 HODE_DEV float pow_hill(float x, float p) {
@@ -215,6 +227,36 @@ struct GradAcc {
     for (int i = 0; i < kNTheta; ++i) dth[i] = 0.f;
   }
 };
+
+// Fold the per-lane parameter gradients over the patients of this wave and store the wave's partial row [w1 | b1 | theta]
+// (an idle lane's cotangents are zero, so it adds zeros).  Quad layout: lane q < 4 stores the rows of its slice; in the
+// ragged layout a padding slot (row >= M) is not written, since its index lies in the bias / theta part.  Every lane of a
+// patient holds the same expert gradient, so quad position 0 alone is counted.
+template <int D, int LPP, bool NEED_TH>
+HODE_DEV void store_grad_partials(const GradAcc<D, LPP>& acc, float* __restrict__ out) {
+  using Ml = MlSlice<D, LPP>;
+  constexpr int M = D - 4;
+  constexpr int MR = Ml::MR;
+  const int lane = threadIdx.x & 63;
+  if constexpr (M > 0) {
+#pragma unroll
+    for (int r = 0; r < MR; ++r) {
+      const bool mine = lane < LPP && (!Ml::kRagged || lane * MR + r < M);
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        const float v = wave_sum_patients<LPP>(acc.dw[r][i]);
+        if (mine) out[(lane * MR + r) * D + i] = v;
+      }
+      const float vb = wave_sum_patients<LPP>(acc.db[r]);
+      if (mine) out[M * D + lane * MR + r] = vb;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kNTheta; ++i) {
+    const float v = wave_sum_patients<LPP>(NEED_TH ? acc.dth[i] : 0.f);
+    if (lane == 0) out[M * D + M + i] = v;
+  }
+}
 
 // Vector-Jacobian product of the rhs at (t, Y): a = (df/dY)^T g, and parameter-gradient accumulation.
 //   own_s : this lane's tanh outputs at Y (from roche_rhs), g : cotangent of k (full, all lanes), q : quad position.

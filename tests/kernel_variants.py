@@ -147,7 +147,7 @@ def roche_fixed(D, lanes, method, ablate, need_theta, tape=True, T=8, B=77):
     """Fixed-grid Roche forward + backward as hode.plan.RocheRKPlan launches them (tape = HODE_FLAG_TAPE).
     split: csrc/hode_rk_split.hip:1133-1168 split_method / split_bwd_method (the tape pointer selects TAPE, need_theta_grad
     NEED_TH) and the fold :1228.  mf: csrc/hode_rk_mf.hip:554-575 mf_launch / mf_dim and the fold :597.  lane kernels:
-    csrc/hode_rk_kernels.hpp:344 dispatch_lpp (LPP 4 only where (D-4) % 4 == 0), :327 dispatch_method, :320 launch_bwd."""
+    csrc/hode_rk_kernels.hpp:384 dispatch_lpp (LPP 4 only where (D-4) % 4 == 0), :368 dispatch_method, :360 launch_bwd."""
     lay = roche_layout(D, lanes, T)
     a, nt = _b(ablate), _b(need_theta)
     if lay == "split":
@@ -338,11 +338,11 @@ def roche_body(ablate, theta0, theta1, K):
         if (hill2 && a.K == 1) body<..., HILL2 = true, K1 = true>     "hill2_k1"  x * x, one dose time in a register
         else if (hill2)        body<..., HILL2 = true, K1 = false>    "hill2_kn"  x * x, loop over K dose times
         else                   body<..., HILL2 = false, K1 = false>   "general"   powf / log_f32, loop over K dose times
-    csrc/hode_rk_kernels.hpp:122-126 (rk_fwd_kernel), :299-302 (rk_bwd_kernel); csrc/hode_rk_split.hip:1115-1118
+    csrc/hode_rk_kernels.hpp:136-140 (rk_fwd_kernel), :339-342 (rk_bwd_kernel); csrc/hode_rk_split.hip:1115-1118
     (split_bwd_kernel), :1123-1126 (split_fwd_kernel); csrc/hode_rk_mf.hip:245-248 (mf_fwd_kernel), :498-501
-    (mf_bwd_kernel); csrc/hode_dopri5_kernels.hpp:886-889 (dp_persist_kernel), :896-906 (dp_fwd_kernel; its attempt
-    launches take hill2 from the host's read-back of the same comparison, csrc/hode_dopri5.hip:174-180), :1395-1403
-    (dp_bwd_kernel), :1536-1539 (dp_initbwd_kernel).  ABLATE forces hill2: the ablate rhs has no Hill terms."""
+    (mf_bwd_kernel); csrc/hode_dopri5_kernels.hpp:876-879 (dp_persist_kernel), :886-896 (dp_fwd_kernel; its attempt
+    launches take hill2 from the host's read-back of the same comparison, csrc/hode_dopri5.hip:174-180), :1361-1369
+    (dp_bwd_kernel), :1502-1505 (dp_initbwd_kernel).  ABLATE forces hill2: the ablate rhs has no Hill terms."""
     hill2 = bool(ablate) or (theta0 == 2.0 and theta1 == 2.0)
     if hill2:
         return "hill2_k1" if K == 1 else "hill2_kn"

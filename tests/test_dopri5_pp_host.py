@@ -66,10 +66,11 @@ def test_the_device_code_is_compiled_not_copied():
     """The rhs, its VJP, the stages, the step factor, the tableau and the partial rows are the existing headers' own."""
     src = open(os.path.join(build_hip.CSRC, "dopri5_pp", "hode_dopri5_pp_kernels.hpp")).read()
     for name in ("roche_rhs<", "roche_vjp<", "GradAcc<", "MlSlice<", "DoseSched<", "load_theta(", "dp_stages<", "dp_step_factor(",
-                 "dp_store_grad_partials<", "dp_load_dose<", "kDpErr[", "kDpMid[", "kDpBeta[", "LaneMap<1>"):
+                 "store_grad_partials<", "load_dose<", "kDpErr[", "kDpMid[", "kDpBeta[", "LaneMap<1>"):
         assert name in src, name
     for definition in ("HODE_DEV void roche_rhs", "HODE_DEV void roche_vjp", "HODE_DEV void dp_stages", "HODE_DEV double dp_step_factor",
-                       "constexpr float kDp", "struct GradAcc", "HODE_DEV void dp_store_grad_partials", "fold_partials_kernel"):
+                       "constexpr float kDp", "struct GradAcc", "HODE_DEV void store_grad_partials", "DoseSched<K1> load_dose(", "dp_store_grad_partials", "dp_load_dose",
+                       "pp_load_dose", "fold_partials_kernel"):
         assert definition not in src, definition
     host = open(os.path.join(build_hip.CSRC, "dopri5_pp", "hode_dopri5_pp.hip")).read()
     assert "launch_fold_partials(" in host and "hode_side_error.hpp" in host and "__global__" not in host

@@ -75,14 +75,23 @@ def test_the_first_table_is_as_it_was_and_the_row_is_in_the_second():
 
 
 def test_the_device_code_is_compiled_not_copied():
-    """The rhs, its VJP, the dose schedule, the stage times, the lane map and the fold are the existing headers' own."""
+    """The sweep is the fixed-grid adjoint's own, instantiated with the dose hook: the rhs, its VJP, the dose schedule, the
+    stage times, the stage algebra, the lane map and the fold are the existing headers' code and are not restated."""
     src = open(os.path.join(build_hip.CSRC, "dose", "hode_dose_kernels.hpp")).read()
-    for name in ("roche_rhs<", "roche_vjp<", "GradAcc<", "MlSlice<", "DoseSched<", "load_theta(", "load_dose<", "StageTimes st(",
-                 "LaneMap<1>", "n_partials<D, 1>()", "load_vec<D>", "store_vec<D, 1>", "wave_sum("):
+    for name in ("rk_bwd_body<D, 1, METHOD, ABLATE,", "DoseSched<", "DoseVal", "LaneMap<1>", "RkArgs", "kGrad = true"):
         assert name in src, name
     for definition in ("HODE_DEV void roche_rhs", "HODE_DEV void roche_vjp", "struct GradAcc", "struct DoseSched", "struct StageTimes",
-                       "struct LaneMap", "fold_partials_kernel", "struct RkArgs"):
+                       "struct LaneMap", "fold_partials_kernel", "struct RkArgs", "HODE_DEV void rk_bwd_body", "roche_vjp<", "roche_rhs<",
+                       "0.375f", "kOneThird", "wave_sum(", "StageTimes st(", "load_vec<", "store_vec<", "GradAcc<"):
         assert definition not in src, definition
+    # what the dose header used to name itself is what the shared sweep names
+    sweep = open(os.path.join(build_hip.CSRC, "hode_rk_kernels.hpp")).read()
+    sweep = sweep[sweep.index("struct NoDoseGrad"):sweep.index("void rk_bwd_kernel")]
+    for name in ("roche_rhs<", "roche_vjp<", "GradAcc<", "MlSlice<", "DoseSched<", "load_theta(", "load_dose<", "StageTimes st(",
+                 "LaneMap<LPP>", "n_partials<D, LPP>()", "load_vec<D>", "store_vec<D, LPP>", "wave_sum(", "class DOSE = NoDoseGrad"):
+        assert name in sweep, name
+    assert sweep.count("if constexpr (DOSE::kGrad) dose.tap(") == sweep.count("roche_vjp<") == 7  # every stage VJP is tapped
+    assert sweep.count("stage_dose(dose, ds, ") == 5 and sweep.count("ds.at(") == 1  # ... and every stage dose is the hook's (ds.at: stage_dose itself)
     host = open(os.path.join(build_hip.CSRC, "dose", "hode_dose.hip")).read()
     assert "launch_fold_partials(" in host and "patients_per_wave(" in host and "hode_side_error.hpp" in host and "__global__" not in host
     files = build_hip.digest_files(LIB)
