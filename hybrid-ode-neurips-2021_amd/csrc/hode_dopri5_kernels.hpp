@@ -50,7 +50,8 @@ struct DpArgs {
   float* __restrict__ h;
   DpCtrl* ctrl;            // [2]
   DpInit* init;            // [1]
-  float* partials;         // [2][2 * n_waves]
+  float* partials;         // [2][2 * n_waves]: even slots the error-norm partials; the odd slots of the second half carry
+                           // init1's non-finite-start-state flags (read by init2 only), the other odd slots init1's s1
   unsigned long long* slots;  // [2][n_waves]: (sequence number << 32 | error-norm partial) of the persistent attempt loop
   int max_iters;           // persistent attempt loop: attempts this launch may run
   float* kbuf;             // [7][B][D]
@@ -154,20 +155,27 @@ HODE_DEV void dp_init1_body(const DpArgs& a) {
   store_vec<D, LPP>(a.tape_y + (size_t)lm.p * D, y, lm.q, lm.live);
   store_vec<D, LPP>(a.kbuf + (size_t)lm.p * D, f0, lm.q, lm.live);
   float s0 = 0.f, s1 = 0.f;
+  bool bad = false;
 #pragma unroll
   for (int c = 0; c < D; ++c) {
     const float scale = a.atol + __builtin_fabsf(y[c]) * a.rtol;
     const float u = div_f32(y[c], scale), v = div_f32(f0[c], scale);
     s0 = __builtin_fmaf(u, u, s0);
     s1 = __builtin_fmaf(v, v, s1);
+    bad |= !__builtin_isfinite(y[c]);
   }
   const float m = (lm.live && lm.q == 0) ? 1.0f : 0.0f;  // count every patient once
   s0 = wave_sum(s0 * m);
   s1 = wave_sum(s1 * m);
+  const bool wave_bad = __builtin_amdgcn_ballot_w64(bad && lm.live) != 0;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if ((threadIdx.x & 63) == 0) {
     a.partials[2 * wave] = s0;
     a.partials[2 * wave + 1] = s1;
+    // A non-finite start state makes d0, and with it dt_0, NaN: the dt check of attempt 0 would report an underflow before
+    // any attempt looks at the state.  The wave's flag travels in the odd slot of the second half, which no other launch
+    // uses (init2 and the attempts write the even ones); init2 seeds the controller's status word from it.
+    a.partials[2 * a.n_waves + 2 * wave + 1] = wave_bad ? 1.0f : 0.0f;
   }
 }
 
@@ -183,6 +191,7 @@ HODE_DEV void dp_init2_body(const DpArgs& a) {
   const float cnt = (float)a.B * (float)D;
   const float d0 = __builtin_sqrtf(fold_waves(a.partials, a.n_waves, 2, 0) / cnt);
   const float d1 = __builtin_sqrtf(fold_waves(a.partials, a.n_waves, 2, 1) / cnt);
+  const float bad0 = fold_waves(a.partials + (size_t)2 * a.n_waves, a.n_waves, 2, 1);  // init1's non-finite flags
   const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : div_f32(0.01f * d0, d1);
   float y[D], f0[D], y1[D], f1[D], own[Ml::MR];
   load_vec<D>(a.y0 + (size_t)lm.p * D, y);
@@ -208,7 +217,8 @@ HODE_DEV void dp_init2_body(const DpArgs& a) {
     c.dt = 0.0;
     c.h0 = h0;
     c.d1 = d1;
-    c.n_acc = 0; c.n_rej = 0; c.j_next = 1; c.done = (a.T <= 1) ? 1 : 0; c.status = 0; c.attempt = 0;
+    c.n_acc = 0; c.n_rej = 0; c.j_next = 1; c.done = (a.T <= 1) ? 1 : 0; c.attempt = 0;
+    c.status = bad0 != 0.0f ? HODE_STATUS_NONFINITE : 0;  // attempt 0 stops on it before it looks at dt_0
     a.ctrl[0] = c;
     a.ctrl[1] = c;  // defined contents for the record attempt 0 will fill (its status word is OR-ed into)
     DpInit in{};

@@ -16,7 +16,7 @@ struct NdpArgs {
   NeuralArgs nn;  // t, y0, dosage, dose_times, w1, b1, b2, w2, h, grad_h, grad_y0, B, T, K
   DpCtrl* ctrl;
   DpInit* init;
-  float* partials;       // [4 * n_waves]
+  float* partials;       // [4 * n_waves], as DpArgs::partials: the odd slots of the second half carry init1's non-finite flags
   float* kbuf;           // [7][B][D]
   double* tape_t;
   double* tape_dt;
@@ -97,9 +97,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     mf_store_rows<D>(a.kbuf + poff, g, f0, L.live);
     const v4 sc = ndp_scale<D>(a, y);
     const float s0 = wave_sum(ndp_sq_ratio<D>(L, y, sc)), s1 = wave_sum(ndp_sq_ratio<D>(L, f0, sc));
+    bool bad = false;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bad |= L.valid[r] != 0.0f && !__builtin_isfinite(y[r]);
+    const bool wave_bad = __builtin_amdgcn_ballot_w64(bad && L.live) != 0;
     if (L.lane == 0) {
       a.partials[2 * L.wave] = s0;
       a.partials[2 * L.wave + 1] = s1;
+      // a non-finite start state (dp_init1_body): the wave's flag, in the slot no other launch uses
+      a.partials[2 * a.n_waves + 2 * L.wave + 1] = wave_bad ? 1.0f : 0.0f;
     }
   } else if constexpr (PHASE == 1) {
     // init2: h0 from (d0, d1); f1 = f(t0 + h0, y0 + h0 f0); partial of ((f1 - f0)/scale)^2; lane 0 seeds the controller
@@ -107,6 +113,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     nn.load(a.nn, L.lane);
     const float d0 = __builtin_sqrtf(fold_waves(a.partials, a.n_waves, 2, 0) / cnt);
     const float d1 = __builtin_sqrtf(fold_waves(a.partials, a.n_waves, 2, 1) / cnt);
+    const float bad0 = fold_waves(a.partials + (size_t)2 * a.n_waves, a.n_waves, 2, 1);  // init1's non-finite flags
     const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : div_f32(0.01f * d0, d1);
     const v4 y = mf_load_rows<D>(a.nn.y0 + poff, g);
     const v4 f0 = mf_load_rows<D>(a.kbuf + poff, g);
@@ -121,7 +128,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       c.dt = 0.0;
       c.h0 = h0;
       c.d1 = d1;
-      c.n_acc = 0; c.n_rej = 0; c.j_next = 1; c.done = (a.nn.T <= 1) ? 1 : 0; c.status = 0; c.attempt = 0;
+      c.n_acc = 0; c.n_rej = 0; c.j_next = 1; c.done = (a.nn.T <= 1) ? 1 : 0; c.attempt = 0;
+      c.status = bad0 != 0.0f ? HODE_STATUS_NONFINITE : 0;  // attempt 0 stops on it before it looks at dt_0
       a.ctrl[0] = c;
       a.ctrl[1] = c;
       DpInit in{};

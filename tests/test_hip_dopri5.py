@@ -224,9 +224,12 @@ def test_dopri5_failure_is_a_runtime_error():
     theta = torch.tensor(THETA_DEFAULT + (0.0,) * 3, device=dev)
     y0 = inp["z0"].to(dev)
     y0[2, 1] = float("nan")
-    with pytest.raises(RuntimeError):
+    adaptive.last_stats.update(n_accepted=-1)
+    with pytest.raises(hode.HodeError) as e:  # a RuntimeError: the reference's training loop catches it
         adaptive.roche_dopri5(y0, theta, f.ml_net[0].weight.detach().to(dev), f.ml_net[0].bias.detach().to(dev),
-                              inp["t"].to(dev), dosage.to(dev), times.to(dev), rtol=1e-7, atol=1e-8)
+                              inp["t"].to(dev), dosage.to(dev), times.to(dev), rtol=1e-7, atol=1e-8, max_steps=64)
+    assert isinstance(e.value, RuntimeError) and str(e.value) == "hode dopri5: non-finite values in state `y`"
+    assert adaptive.last_stats["n_accepted"] == 0  # the start state is refused: no step is taken from it
 
 
 @pytest.mark.parametrize("variant", ["ablate", "general_hill", "two_doses", "tail_lanes"])

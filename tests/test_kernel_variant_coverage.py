@@ -24,15 +24,21 @@ BUILD = os.path.join(CSRC, "build")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-@pytest.fixture(scope="module")
-def all_compiled():
-    """Every kernel symbol (`.kd`) of the library's object files."""
-    objs = sorted(glob.glob(os.path.join(BUILD, "*.o")))
+def compiled_kernel_names(obj_dir=BUILD):
+    """Every kernel symbol (`.kd`) of the object files in `obj_dir` (libhode.so's by default), as kv.kernel_name spells it.
+    tests/test_failure_cases.py reads both solver libraries with it."""
+    objs = sorted(glob.glob(os.path.join(obj_dir, "*.o")))
     objs = [o for o in objs if "__" not in os.path.basename(o)]  # experiment builds (build_hip.build_variant)
     if not objs:
         pytest.skip("object files are not in the tree (library shipped pre-built)")
     from kernel_descriptor import kernel_descriptors
     return {kv.kernel_name(dem) for o in objs for dem, _ in kernel_descriptors(o)}
+
+
+@pytest.fixture(scope="module")
+def all_compiled():
+    """Every kernel symbol (`.kd`) of the library's object files."""
+    return compiled_kernel_names()
 
 
 @pytest.fixture(scope="module")
