@@ -1,6 +1,7 @@
 // The body of the LSTM window kernels (hode_lstm_kernels.hpp), included once per kernel definition: lstm_fwd_kernel with
 // `using POLICY = LstmFinalState`, lstm_seq_fwd_kernel with LstmSequence.  In scope where it is included: the template
-// arguments NT, TPW, NW, VEC4, the kernel argument `LstmArgs p` and POLICY.  Not a header of its own: no include guard.
+// arguments NT, TPW, NW, VEC4, PAD, the kernel argument `LstmArgs p` and POLICY; PAD: the hidden size is not a compiled
+// one, units H .. Hp - 1 are padding.  Not a header of its own: no include guard.
   constexpr int NTHR = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int BT = 16 * NT;
@@ -245,7 +246,11 @@
         const float cn = __builtin_fmaf(gf, cst[tt][c], gi * gg);
         const float hn = go * tanh_f32(cn);
         cst[tt][c] = cn;
-        nxt_lane[4 * tt * LD + 16 * c] = hn;
+        // PAD (H < Hp): a padded unit (u >= H: zero weights, zero bias) stores an exact zero, by a select.  Its
+        // pre-activations are 0 * act, which is NaN, not 0, for a patient whose measurement or action is infinite, and the
+        // next step would multiply that h by the zero-padded W_hh column -- 0 * NaN -- into every real unit of the patient,
+        // where the gates of the real units only saturate (sigmoid -> 0 / 1, tanh -> +-1) and h stays finite
+        nxt_lane[4 * tt * LD + 16 * c] = (PAD && u >= p.H) ? 0.f : hn;
         if constexpr (POLICY::kAllSteps) {
           if (u < p.H && 16 * c + pc < nvalid) hs_lane[16 * c * p.H + 4 * tt] = hn;   // padded units, patients past the batch: never written
         }

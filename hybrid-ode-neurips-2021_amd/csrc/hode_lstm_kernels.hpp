@@ -62,6 +62,10 @@ HODE_DEV float sigmoid_gate(float x) {
 // NW waves of TPW 16-row tiles each (NW * TPW * 16 = padded H).  Hp = 160 runs as 8 waves x 5 tiles: two waves per
 // SIMD, every register in the 256-entry VGPR file -- with 4 x 10 the 120 accumulators went to the AGPR half and came
 // back through v_accvgpr moves every step, the compiler spilled, and nothing covered a non-MFMA instruction.
+// PAD: the hidden size is not a compiled one (H < Hp): the cell update zeroes h of the padded units H .. Hp - 1 by a select
+// (hode_lstm_fwd_body.hpp says why).  A template parameter, so that the kernels of H == Hp (every shipped encoder) are the
+// code they were: as a select on every store lstm_fwd_kernel ran 1.7 % longer at the benchmark's H = 160 (3.57 against
+// 3.52 ms), as a pass of its own behind the update loop 3.2 %, as two copies of the body under a kernel-uniform branch 2.8 %.
 // VEC4: obs_dim % 4 == 0 (x tile fetched in 16-byte groups).  A compile-time switch: as a run-time branch the flat
 // path's per-element divisions are hoisted out of the step loop and pinned ~60 registers in every shipped shape.
 //
@@ -80,7 +84,7 @@ HODE_DEV float sigmoid_gate(float x) {
 struct LstmFinalState { static constexpr bool kAllSteps = false; };
 struct LstmSequence { static constexpr bool kAllSteps = true; };
 
-template <int NT, int TPW, int NW, bool VEC4>
+template <int NT, int TPW, int NW, bool VEC4, bool PAD>
 __global__ __launch_bounds__(64 * NW) void lstm_fwd_kernel(LstmArgs p) {
   using POLICY = LstmFinalState;
 #include "hode_lstm_fwd_body.hpp"
@@ -88,7 +92,7 @@ __global__ __launch_bounds__(64 * NW) void lstm_fwd_kernel(LstmArgs p) {
 
 #ifdef HODE_LSTM_SEQ_UNIT
 // libhode_lstm_seq.so only: p.h_out is [T][B][H]
-template <int NT, int TPW, int NW, bool VEC4>
+template <int NT, int TPW, int NW, bool VEC4, bool PAD>
 __global__ __launch_bounds__(64 * NW) void lstm_seq_fwd_kernel(LstmArgs p) {
   using POLICY = LstmSequence;
 #include "hode_lstm_fwd_body.hpp"

@@ -28,19 +28,25 @@ constexpr int kFwdNW = kTPW <= 5 ? 4 : 8;
 constexpr int kFwdTPW = kTPW <= 5 ? kTPW : kTPW / 2;
 static_assert(kFwdTPW * kFwdNW == kTPW * 4, "forward geometry must cover the padded hidden size");
 
-template <int NT, bool VEC4>
+template <int NT, bool VEC4, bool PAD>
 int launch_fwd_vec(const LstmGeom& G, const LstmArgs& a, hipStream_t s) {
-  if (int e = hode::hip_fail(hipFuncSetAttribute((const void*)HODE_LSTM_FWD_KERNEL<NT, kFwdTPW, kFwdNW, VEC4>,
+  if (int e = hode::hip_fail(hipFuncSetAttribute((const void*)HODE_LSTM_FWD_KERNEL<NT, kFwdTPW, kFwdNW, VEC4, PAD>,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)G.lds_bytes),
                              "hipFuncSetAttribute(MaxDynamicSharedMemorySize)"))
     return e;
-  hipLaunchKernelGGL((HODE_LSTM_FWD_KERNEL<NT, kFwdTPW, kFwdNW, VEC4>), dim3(G.nblk), dim3(64 * kFwdNW), G.lds_bytes, s, a);
+  hipLaunchKernelGGL((HODE_LSTM_FWD_KERNEL<NT, kFwdTPW, kFwdNW, VEC4, PAD>), dim3(G.nblk), dim3(64 * kFwdNW), G.lds_bytes, s, a);
   return hode::hip_fail(hipGetLastError(), "lstm_fwd launch");
+}
+
+// PAD: padded hidden units (H is not a compiled size)
+template <int NT, bool VEC4>
+int launch_fwd_pad(const LstmGeom& G, const LstmArgs& a, hipStream_t s) {
+  return a.H == 16 * kTPW ? launch_fwd_vec<NT, VEC4, false>(G, a, s) : launch_fwd_vec<NT, VEC4, true>(G, a, s);
 }
 
 template <int NT>
 int launch_fwd_one(const LstmGeom& G, const LstmArgs& a, hipStream_t s) {
-  return (a.OBS & 3) == 0 ? launch_fwd_vec<NT, true>(G, a, s) : launch_fwd_vec<NT, false>(G, a, s);
+  return (a.OBS & 3) == 0 ? launch_fwd_pad<NT, true>(G, a, s) : launch_fwd_pad<NT, false>(G, a, s);
 }
 
 template <int NT, bool FLAT>

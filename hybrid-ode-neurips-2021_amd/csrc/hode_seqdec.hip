@@ -67,6 +67,17 @@ HODE_DEV void store_tile(float* __restrict__ dst, int j, int g, int D, const v4&
   }
 }
 
+// rows 16 j + 4 g + r < n keep their value, the padding rows become an exact 0.  A select, not a product: a padding row of a
+// gate product is 0 * input, which is NaN -- not 0 -- for a patient whose action or state is infinite, and the next
+// product would multiply it by a zero-padded weight column (0 * NaN) into every real row of that patient, where the
+// reference's gates only saturate (sigmoid -> 0 / 1, tanh -> +-1).  On finite data the padding rows are 0 either way.
+HODE_DEV v4 keep_rows(const v4& v, int j, int g, int n) {
+  v4 o;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) o[r] = 16 * j + 4 * g + r < n ? v[r] : 0.f;
+  return o;
+}
+
 // which registers of the input tiles carry the action (row D), the time feature (row D + 1) and the constant 1 (row D + 2)
 template <int KT>
 struct InputRows {
@@ -249,7 +260,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         hc[e] = o * tanh_f32(cc[e]);
       }
       c[u] = cat4(cc[0], cc[1]);
-      h[u] = cat4(hc[0], hc[1]);
+      h[u] = keep_rows(cat4(hc[0], hc[1]), u, g, D);   // the next step's input: padding rows exactly 0
       store_tile(s.h + k * step + (size_t)p * D, u, g, D, h[u], live);
       if (s.c) store_tile(s.c + k * step + (size_t)p * D, u, g, D, c[u], live);
     }
@@ -326,10 +337,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         dzo[e] = (dhe * tc) * (o * (one - o));
         dcp[e] = dce * f;
       }
-      dz[u] = cat4(dzi[0], dzi[1]);
-      dz[HT + u] = cat4(dzf[0], dzf[1]);
-      dz[2 * HT + u] = cat4(dzg[0], dzg[1]);
-      dz[3 * HT + u] = cat4(dzo[0], dzo[1]);
+      // padding rows exactly 0 (keep_rows): their recomputed gates are 0 * input, and W_hh^T's zero columns would carry a
+      // NaN from there into dh of every real unit
+      dz[u] = keep_rows(cat4(dzi[0], dzi[1]), u, g, D);
+      dz[HT + u] = keep_rows(cat4(dzf[0], dzf[1]), u, g, D);
+      dz[2 * HT + u] = keep_rows(cat4(dzg[0], dzg[1]), u, g, D);
+      dz[3 * HT + u] = keep_rows(cat4(dzo[0], dzo[1]), u, g, D);
       dc[u] = cat4(dcp[0], dcp[1]);
     }
     mfma_product(bw.W, dz, dh);
@@ -414,7 +427,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 #pragma unroll
     for (int j = 0; j < KT; ++j) {
       z[j] = sigmoid4(z[j]);
-      zx[j] = z[j] * x[j];
+      zx[j] = keep_rows(z[j] * x[j], j, g, D + 2);   // rows past [init, a, tau]: exactly 0, not sigmoid(0 * inf) * 0
     }
     mfma_product(fw.N, zx, nn);
 #pragma unroll

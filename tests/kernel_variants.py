@@ -260,13 +260,13 @@ def lstm_geom(H, obs, B, save_tape, patient_tiles=0):
 
 def lstm_kernels(H, obs, B, save_tape, patient_tiles=0):
     """hode_lstm_fwd (csrc/hode_lstm.hip:169 lstm_pack_kernel, then csrc/hode_lstm_tpw.hip:33-35
-    lstm_fwd_kernel<NT, fTPW, fNW, VEC4 = obs % 4 == 0>); with the tape (hode.lstm.lstm_encode) also hode_lstm_bwd
+    lstm_fwd_kernel<NT, fTPW, fNW, VEC4 = obs % 4 == 0, PAD = H != 16 TPW>, csrc/hode_lstm_tpw.hip launch_fwd_pad); with the tape (hode.lstm.lstm_encode) also hode_lstm_bwd
     (csrc/hode_lstm.hip:217 lstm_pack_hh_kernel, csrc/hode_lstm_tpw.hip:47-49 lstm_bwd_kernel<NT, TPW, FLAT = H == 16 TPW>)
     and hode_lstm_fill_operand (csrc/hode_lstm.hip:268-274 lstm_fill_operand_kernel<VEC4>: obs % 4 == 0 and 16-byte
     aligned x / mask / h_prev, which fresh tensors are)."""
     _, tpw, ftpw, fnw, nt = lstm_geom(H, obs, B, save_tape, patient_tiles)
     vec4 = _b(obs % 4 == 0)
-    out = ["hode::lstm_pack_kernel", "hode::lstm_fwd_kernel<%d, %d, %d, %s>" % (nt, ftpw, fnw, vec4)]
+    out = ["hode::lstm_pack_kernel", "hode::lstm_fwd_kernel<%d, %d, %d, %s, %s>" % (nt, ftpw, fnw, vec4, _b(H != 16 * tpw))]
     if save_tape:
         out += ["hode::lstm_pack_hh_kernel", "hode::lstm_bwd_kernel<%d, %d, %s>" % (nt, tpw, _b(H == 16 * tpw)),
                 "hode::lstm_fill_operand_kernel<%s>" % vec4]
@@ -573,8 +573,9 @@ LSTM_OBS_VEC4, LSTM_OBS_ODD = 20, 23
 
 def _lstm_cases():
     """Per padded hidden size (TPW): the tape path (lstm_encode) at NT 1, 2, 3 once with H = 16 TPW and obs % 4 != 0,
-    once with H = 16 TPW - 3 and obs % 4 == 0 -- every (NT, FLAT) backward and (NT, VEC4) forward -- and the no-tape path
-    (lstm_final_state) at NT = 4 with both obs; NT forced by patient_tiles on a batch ragged against 16 NT, T = 3 or 4.
+    once with H = 16 TPW - 3 and obs % 4 == 0 -- every (NT, FLAT) backward -- and the no-tape path (lstm_final_state) at
+    NT = 4 with both obs; NT forced by patient_tiles on a batch ragged against 16 NT, T = 3 or 4.  Then the no-tape path at
+    every NT with the other obs of each, so that every (NT, VEC4, PAD) forward runs (PAD = padded hidden units).
     Then NT chosen by choose_nt from the batch size alone (1: B = 100; 2: 4097; 3: 8193; 4: 12289 without a tape), the
     staging clamp (obs = 100 lowers a forced NT = 4 to 3, at the largest hidden size too), and B = 1 / T = 1 calls."""
     out = []
@@ -585,6 +586,14 @@ def _lstm_cases():
                 H = 16 * tpw if flat else 16 * tpw - 3
                 obs = (LSTM_OBS_ODD if flat else LSTM_OBS_VEC4) if tape else (LSTM_OBS_VEC4 if flat else LSTM_OBS_ODD)
                 out.append(dict(family="lstm", H=H, obs=obs, B=32 * nt + 5 + j, T=3 + (j + nt + flat) % 2, tape=tape, nt=nt))
+    # the forward's PAD (padded hidden units: H != 16 TPW) with the other obs, so that every (NT, VEC4, PAD) forward runs
+    for j, tpw in enumerate(LSTM_TPWS):
+        for nt in (1, 2, 3, 4):
+            for flat in (True, False):
+                tape = nt <= 3
+                obs = (LSTM_OBS_VEC4 if flat else LSTM_OBS_ODD) if tape else (LSTM_OBS_ODD if flat else LSTM_OBS_VEC4)
+                out.append(dict(family="lstm", H=16 * tpw if flat else 16 * tpw - 5, obs=obs, B=32 * nt + 3 + j, T=3 + (j + nt) % 2,
+                                tape=False, nt=nt))
     for B, tape in ((100, True), (4097, True), (8193, True), (100, False), (4097, False), (8193, False), (12289, False)):
         out.append(dict(family="lstm", H=13, obs=LSTM_OBS_VEC4, B=B, T=3, tape=tape, nt=None))
     for H in (40, 150):
@@ -633,7 +642,8 @@ def instantiations():
         fnw = 4 if tpw <= 5 else 8
         for nt in (1, 2, 3, 4):
             for v in (True, False):
-                out.add("hode::lstm_fwd_kernel<%d, %d, %d, %s>" % (nt, 4 * tpw // fnw, fnw, _b(v)))
+                for pad in (True, False):
+                    out.add("hode::lstm_fwd_kernel<%d, %d, %d, %s, %s>" % (nt, 4 * tpw // fnw, fnw, _b(v), _b(pad)))
                 if nt <= 3:
                     out.add("hode::lstm_bwd_kernel<%d, %d, %s>" % (nt, tpw, _b(v)))
     out.update(["hode::lstm_pack_kernel", "hode::lstm_pack_hh_kernel", "hode::lstm_fill_operand_kernel<true>",

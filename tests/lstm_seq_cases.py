@@ -3,13 +3,14 @@ LSTM window kernels under their all-steps policy (h of every step out, a cotange
 independently of the library, which kernel a call launches.  The geometry is the one csrc/hode_lstm.hip computes for
 libhode.so too (the host code is compiled twice), restated in tests/kernel_variants.py lstm_geom: the padded hidden size
 Hp = 16 TPW, the forward's fNW waves of fTPW tiles, NT forced by patient_tiles (1 .. 4 without a tape, 1 .. 3 with one).
-    forward    lstm_pack_kernel, lstm_seq_fwd_kernel<NT, fTPW, fNW, VEC4 = obs % 4 == 0>
+    forward    lstm_pack_kernel, lstm_seq_fwd_kernel<NT, fTPW, fNW, VEC4 = obs % 4 == 0, PAD = H != 16 TPW>
     backward   lstm_pack_hh_kernel, lstm_seq_bwd_kernel<NT, TPW, FLAT = H == 16 TPW>, lstm_fill_operand_kernel<VEC4>
 
 Not a cross product.  Every case has a batch ragged against its tile, B = 32 NT + 5 (more than one workgroup, the last one
 partly filled).  FWD_CASES (forward only, no tape): every (TPW, NT 1 .. 4, VEC4); along the way T in 1 (no recurrence), 3
 (the first shape with a middle step), 4; H = 16 TPW and 16 TPW - 3 (padded units); obs 20 / 23; with and without `a`, with
-and without `mask`, both directions.  BWD_CASES (forward with the tape + backward, T = 4): every (TPW, NT 1 .. 3, FLAT),
+and without `mask`, both directions; PAD_FWD_CASES: the same calls with the other H of each, so that every forward runs with
+and without padded hidden units.  BWD_CASES (forward with the tape + backward, T = 4): every (TPW, NT 1 .. 3, FLAT),
 both directions, obs 20 / 23."""
 import kernel_variants as kv
 
@@ -53,7 +54,15 @@ def _bwd_cases():
     return out
 
 
+def _pad_fwd_cases():
+    """FWD_CASES pairs every (TPW, NT, VEC4) with one of H = 16 TPW and 16 TPW - 3; these are the other ones, so that every
+    forward runs with and without padded hidden units (the kernels' PAD)."""
+    return [_case(-(-c["H"] // 16), c["nt"], c["H"] % 16 != 0, c["obs"], 5 if c["T"] == 4 else c["T"], c["a"], c["mask"], c["reverse"], False)
+            for c in _fwd_cases()]   # T = 5 for 4: BWD_CASES hold every T = 4 id
+
+
 FWD_CASES = _fwd_cases()
+PAD_FWD_CASES = _pad_fwd_cases()
 BWD_CASES = _bwd_cases()
 #: the bit-for-bit comparison with lstm_final_state / lstm_encode (libhode.so): a subset over the sizes, both directions
 DIFF_CASES = [c for i, c in enumerate(BWD_CASES) if i % 5 == 0]
@@ -76,7 +85,7 @@ def kernels(c):
     """The kernels of one call of the case: forward, and with a tape also the backward and the operand fill."""
     _, tpw, ftpw, fnw, nt = kv.lstm_geom(c["H"], c["obs"], c["B"], c["tape"], c["nt"])
     vec4 = kv._b(c["obs"] % 4 == 0)
-    out = ["hode::lstm_pack_kernel", "hode::lstm_seq_fwd_kernel<%d, %d, %d, %s>" % (nt, ftpw, fnw, vec4)]
+    out = ["hode::lstm_pack_kernel", "hode::lstm_seq_fwd_kernel<%d, %d, %d, %s, %s>" % (nt, ftpw, fnw, vec4, kv._b(c["H"] != 16 * tpw))]
     if c["tape"]:
         out += ["hode::lstm_pack_hh_kernel", "hode::lstm_seq_bwd_kernel<%d, %d, %s>" % (nt, tpw, kv._b(c["H"] == 16 * tpw)),
                 "hode::lstm_fill_operand_kernel<%s>" % vec4]
@@ -90,10 +99,11 @@ def expected_kernels():
     for tpw in TPWS:
         fnw = 4 if tpw <= 5 else 8
         for v in ("true", "false"):
-            out |= {"hode::lstm_seq_fwd_kernel<%d, %d, %d, %s>" % (nt, 4 * tpw // fnw, fnw, v) for nt in (1, 2, 3, 4)}
+            out |= {"hode::lstm_seq_fwd_kernel<%d, %d, %d, %s, %s>" % (nt, 4 * tpw // fnw, fnw, v, pad) for nt in (1, 2, 3, 4)
+                    for pad in ("true", "false")}
             out |= {"hode::lstm_seq_bwd_kernel<%d, %d, %s>" % (nt, tpw, v) for nt in (1, 2, 3)}
     return out
 
 
 def kernels_reached(cases=None):
-    return {k for c in (FWD_CASES + BWD_CASES if cases is None else cases) for k in kernels(c)}
+    return {k for c in (FWD_CASES + PAD_FWD_CASES + BWD_CASES if cases is None else cases) for k in kernels(c)}

@@ -97,7 +97,21 @@ def _rel(got, want):
 # ------------------------------------------------------------------------------------------------ forward vs float64
 @pytest.mark.parametrize("c", cases.FWD_CASES + cases.BWD_CASES, ids=cases.case_id)
 def test_every_row_and_the_final_cell_state_match_float64(c):
+    _rows_and_cell_state_match_float64(c, _dev())
+
+
+@pytest.mark.parametrize("tpw", cases.TPWS)
+def test_every_row_and_the_final_cell_state_match_float64_with_the_other_hidden_size(tpw):
+    """PAD_FWD_CASES: the forward cases of one padded size again with the other H of each (padded units on / off)."""
     dev = _dev()
+    mine = [c for c in cases.PAD_FWD_CASES if -(-c["H"] // 16) == tpw]
+    assert len(mine) == 8
+    for c in mine:
+        print("case", cases.case_id(c))
+        _rows_and_cell_state_match_float64(c, dev)
+
+
+def _rows_and_cell_state_match_float64(c, dev):
     p = _problem(c)
     h_ref, c_ref = _ref(c, p)
     x, a, m, w = _to(p, dev)

@@ -447,8 +447,9 @@ def test_lstm_rules():
     for H in range(1, 161):
         flat = kv.lstm_kernels(H, 20, 37, True)[3].endswith("true>")
         assert flat == (H in kv.LSTM_SIZES), H
+        assert kv.lstm_kernels(H, 20, 37, True)[1].endswith("false>") == flat, H   # the forward's PAD: the padded sizes again
     for obs in range(1, 41):
-        assert kv.lstm_kernels(16, obs, 37, True)[1].endswith("true>") == (obs % 4 == 0)
+        assert kv.lstm_kernels(16, obs, 37, True)[1].endswith("true, false>") == (obs % 4 == 0)   # VEC4; H = 16: no padded unit
         assert kv.lstm_kernels(16, obs, 37, True)[4].endswith("true>") == (obs % 4 == 0)
     assert [kv.choose_nt(B, True) for B in (1, 4096, 4097, 8193, 12289)] == [1, 1, 2, 3, 2]
     assert [kv.choose_nt(B, False) for B in (1, 4097, 8193, 12289)] == [1, 2, 3, 4]
@@ -471,7 +472,8 @@ def test_lstm_rules():
 def test_lstm_source_pins_the_restated_rules():
     src = _norm(_strip_and_expand(open(os.path.join(CSRC, "hode_lstm_tpw.hip")).read()))
     assert "constexpr int kFwdNW = kTPW <= 5 ? 4 : 8;" in src and "constexpr int kFwdTPW = kTPW <= 5 ? kTPW : kTPW / 2;" in src
-    assert "return (a.OBS & 3) == 0 ? launch_fwd_vec<NT, true>(G, a, s) : launch_fwd_vec<NT, false>(G, a, s);" in src
+    assert "return (a.OBS & 3) == 0 ? launch_fwd_pad<NT, true>(G, a, s) : launch_fwd_pad<NT, false>(G, a, s);" in src
+    assert "return a.H == 16 * kTPW ? launch_fwd_vec<NT, VEC4, false>(G, a, s) : launch_fwd_vec<NT, VEC4, true>(G, a, s);" in src
     assert "return a.H == 16 * kTPW ? launch_bwd_flat<NT, true>(G, a, s) : launch_bwd_flat<NT, false>(G, a, s);" in src
     lh = _norm(_strip_and_expand(open(os.path.join(CSRC, "hode_lstm.hip")).read()))
     assert "static const int kSizes[] = {%s};" % ", ".join(str(v) for v in kv.LSTM_SIZES) in lh

@@ -92,7 +92,7 @@ def test_every_compiled_kernel_is_reached_by_a_gpu_case():
     final-state ones."""
     compiled = _compiled(build_hip.LIBRARIES[LIB].obj)
     want = cases.expected_kernels()
-    assert len(want) == 4 + len(cases.TPWS) * 2 * (4 + 3) == 116
+    assert len(want) == 4 + len(cases.TPWS) * 2 * (2 * 4 + 3) == 180   # forward: NT x VEC4 x PAD; backward: NT x FLAT
     assert compiled == want, (sorted(compiled - want), sorted(want - compiled))
     assert cases.kernels_reached() == compiled
     for group in (cases.DIFF_CASES, cases.MIDDLE_CASES, [cases.AUTOGRAD_CASE], [cases.SENTINEL_CASE]):
@@ -106,6 +106,10 @@ def test_every_compiled_kernel_is_reached_by_a_gpu_case():
 def test_the_case_table_holds_what_it_promises():
     F, B = cases.FWD_CASES, cases.BWD_CASES
     assert len(F) == 64 and len(B) == 48
+    P = cases.PAD_FWD_CASES   # the forward cases again with the other hidden size of each: padded units on / off
+    assert [(c["H"] % 16 == 0, c["obs"], c["nt"], c["reverse"]) for c in P] == [(c["H"] % 16 != 0, c["obs"], c["nt"], c["reverse"]) for c in F]
+    assert {c["T"] for c in P} == {1, 3, 5} and not any(c["tape"] for c in P)
+    assert not {cases.case_id(c) for c in P} & {cases.case_id(c) for c in F + B}
     for c in F + B:
         assert c["B"] == 32 * c["nt"] + 5 and c["obs"] in (20, 23) and c["H"] <= cases.MAX_HIDDEN
     assert all(not c["tape"] and c["T"] in (1, 3, 4) for c in F) and all(c["tape"] and c["T"] == 4 for c in B)
