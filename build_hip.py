@@ -2,8 +2,8 @@
 """Build the gfx950 kernel libraries in-tree with hipcc: `python build_hip.py [-j N] [--force]`.
 
 LIBRARIES has one row per library: its file name in hode/, the directory of its sources, its C ABI header and its compile
-units; MORE_LIBRARIES holds further rows of the same type, and library(name) looks a row up in both.  build() compiles the
-units of all rows in one thread pool (a unit is recompiled when a file of its depfile, its flags
+units; MORE_LIBRARIES and LATER_LIBRARIES hold further rows of the same type, and library(name) looks a row up in all three.
+build() compiles the units of every row (every_library()) in one thread pool (a unit is recompiled when a file of its depfile, its flags
 or this script changed), links each library whose objects are newer than it, and writes digest(<library>) next to it as
 <library>.so.digest; tests and hode/_loader.py compare that stamp with the tree.  The digest covers the header, every source
 of the row's directory, the units' sources and everything they include from inside the tree, the flags and the units."""
@@ -29,6 +29,7 @@ NEURAL_ODD_DIMS = (5, 7, 9, 11, 13, 15)  # csrc/neural_odd/hode_neural_odd_dim.h
 ROCHE_DIMS = (5, 7, 9, 10, 11, 13, 14, 15, 16)  # csrc/roche_dims/: the hybrid decoder beside RK_DIMS / DP_DIMS
 REAL_DIMS_HTS = (1, 2, 3, 4)  # csrc/real_dims/hode_real_dims_ht.hip: hidden tiles of 16 (hidden_dim 1 .. 64)
 REAL_STEP_HTS = (1, 2, 3, 4)  # csrc/real_step/hode_real_step_ht.hip: the same tiles for the one-step-ahead solve
+REAL_DOSE_HTS = (1, 2, 3, 4)  # csrc/real_dose/hode_real_dose_ht.hip: the same tiles for the adjoint with dose-table gradients
 LSTM_TPWS = (1, 2, 3, 4, 5, 6, 8, 10)   # padded hidden sizes 16 * TPW (csrc/hode_lstm_tpw.hip)
 # per-unit flags (measured on MI355X)
 # -fno-slp-vectorize on the split kernels: packed-fp32 pairing costs more v_mov than it saves (step 0.228 -> 0.207 ms)
@@ -102,6 +103,13 @@ def _dopri5_pp_units():
         [("hode_dopri5_pp_d%d" % n, os.path.join(d, "hode_dopri5_pp_dim.hip"), ["-DHODE_DIM=%d" % n]) for n in DP_DIMS]
 
 
+def _real_dose_units():
+    d = os.path.join(CSRC, "real_dose")
+    # -Wno-unused-function: hode_rk_host.hpp is included for the partial fold; its Roche argument helpers are not called here
+    return [("hode_real_dose", os.path.join(d, "hode_real_dose.hip"), ["-Wno-unused-function"])] + \
+        [("hode_real_dose_ht%d" % n, os.path.join(d, "hode_real_dose_ht.hip"), ["-DHODE_REAL_DOSE_HT=%d" % n]) for n in REAL_DOSE_HTS]
+
+
 class Library:
     """One row of LIBRARIES: the file name of the library in hode/ and what it is built from.  `src_dir` and `header` are
     relative to the repository root and use "/", so that digest() is the same wherever the tree lives; `units` is a callable
@@ -148,14 +156,28 @@ MORE_LIBRARIES = {lib.name: lib for lib in (
 )}
 
 
+#: libraries beside both (all_libraries() is pinned by tests/test_dose_host.py), built, linked and stamped with them
+LATER_LIBRARIES = {lib.name: lib for lib in (
+    _multi("real_dose", _real_dose_units),    # the adjoint of the real-data hybrid rhs with dose-table gradients, a unit per hidden-tile count
+)}
+
+
 def library(name):
-    """The row of `name`, from LIBRARIES or MORE_LIBRARIES."""
-    return LIBRARIES[name] if name in LIBRARIES else MORE_LIBRARIES[name]
+    """The row of `name`, from LIBRARIES, MORE_LIBRARIES or LATER_LIBRARIES."""
+    for table in (LIBRARIES, MORE_LIBRARIES):
+        if name in table:
+            return table[name]
+    return LATER_LIBRARIES[name]
 
 
 def all_libraries():
-    """Every row of both tables, in build order."""
+    """Every row of the first two tables, in build order."""
     return list(LIBRARIES.values()) + list(MORE_LIBRARIES.values())
+
+
+def every_library():
+    """Every row of all three tables, in build order: what build() compiles, links and stamps."""
+    return all_libraries() + list(LATER_LIBRARIES.values())
 
 
 OUT = LIBRARIES["libhode.so"].out
@@ -257,7 +279,7 @@ def link(out, objs):
 def build(jobs=7, force=False, verbose=True):
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
         futs = []
-        for lib in all_libraries():
+        for lib in every_library():
             os.makedirs(lib.obj, exist_ok=True)
             futs += [ex.submit(compile_one, n, s, e, force, lib.obj) for n, s, e in lib.units()]
         for f in futs:
@@ -266,7 +288,7 @@ def build(jobs=7, force=False, verbose=True):
                 print("  hipcc %-14s %.1fs" % (name, dt), flush=True)
             if verbose and err.strip():
                 print(err[-2000:], file=sys.stderr)
-    for lib in all_libraries():
+    for lib in every_library():
         objs = [os.path.join(lib.obj, n + ".o") for n, _, _ in lib.units()]
         if force or not os.path.exists(lib.out) or os.path.getmtime(lib.out) < max(os.path.getmtime(o) for o in objs):
             link(lib.out, objs)

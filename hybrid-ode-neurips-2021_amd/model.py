@@ -761,6 +761,33 @@ class LSTMBaseline(nn.Module):
         torch.save({"itr": itr, "state_dict": self.state_dict(), "best_loss": best_loss}, path)
 
 
+class _RocheRealDoseGrad(torch.autograd.Function):
+    """h = odeint(RocheODEReal, y0, t, method) on a fixed grid with a gradient for the dose table act (Ta, B) as well
+    (``RocheODEReal.dose_grad``).  Forward: ``hode.real.real_solve`` under no_grad on detached inputs, so h is bit for bit what
+    the plain call returns at every latent size.  Backward: ``hode.real_dose.real_dose_backward`` (libhode_real_dose.so).
+    Gradients for y0, theta, wflat and act; none for t (its .grad stays None)."""
+
+    @staticmethod
+    def forward(ctx, y0, theta, wflat, t, act, hidden, method, perturb):
+        from hode import real
+        f32c = hode.solver._f32c
+        thc, wc, tc, ac = f32c(theta), f32c(wflat), f32c(t), f32c(act)
+        with torch.no_grad():  # detached inputs: the forward keeps nothing for a backward of its own
+            h = real.real_solve(f32c(y0), thc, wc, tc, ac, hidden, method=method, perturb=perturb, library=None)
+        ctx.save_for_backward(h, thc, wc, tc, ac)
+        ctx.meta = (int(hidden), method, bool(perturb))
+        return h
+
+    @staticmethod
+    def backward(ctx, grad_h):
+        from hode import real_dose
+        h, thc, wc, tc, ac = ctx.saved_tensors
+        hidden, method, perturb = ctx.meta
+        gy0, gth, gw, gact = real_dose.real_dose_backward(h, thc, wc, tc, ac, hode.solver._f32c(grad_h), hidden, method=method,
+                                                          perturb=perturb)
+        return gy0, gth, gw, None, gact, None, None, None
+
+
 class RocheODEReal(nn.Module):
     """Real-data hybrid rhs: two small MLPs for x1, x2, expert x3 / Dose2, GRU-ODE block on the rest (model.py:570-657).
 
@@ -791,6 +818,9 @@ class RocheODEReal(nn.Module):
         self.k_immunity = nn.Parameter(torch.tensor(1, device=self.device, dtype=dtype))
         self.kel = nn.Parameter(torch.tensor(0.2, device=self.device, dtype=dtype))
         self.kel2 = nn.Parameter(torch.tensor(0.2, device=self.device, dtype=dtype))
+        # fixed-grid methods only: True lets a gradient reach the treatment -- with an action that requires grad the solve's
+        # backward fills the gradient of the dose table (hode.real_dose, libhode_real_dose.so)
+        self.dose_grad = False
         self.to(self.device)  # the reference leaves the sub-networks on the default device; everything lives on one here
 
     def set_action_static(self, action, static):
@@ -859,6 +889,13 @@ class RocheODEReal(nn.Module):
         wflat, perturb = self.flat_weights(), bool(options.pop("perturb", False))
         # more than one action column: the reference's sum over dims (0, 2) adds them all into the dose (see the class docstring)
         dose = self.dosage[..., 0] if self.dosage.shape[-1] == 1 else self.dosage.sum(-1)
+        if self.dose_grad and dose.requires_grad and torch.is_grad_enabled():
+            from hode import real_dose
+            real_dose.check_domain(self.latent_dim, self.hidden_dim)  # names the sizes held and libhode_real_dose.so; nothing is loaded or launched before
+            # the column sum above stays a torch op: every column of the action receives the same gradient
+            return substep.solve_with_step_size(
+                lambda grid: _RocheRealDoseGrad.apply(y0, theta, wflat, grid, dose, self.hidden_dim, method, perturb),
+                t, step_size)
         # which library serves this latent size (libhode.so at 4 and 20, libhode_real_dims.so at 5 .. 19) is real_solve's choice
         return substep.solve_with_step_size(
             lambda grid: real.real_solve(y0, theta, wflat, grid, dose, self.hidden_dim, method=method, perturb=perturb, library=None),
@@ -877,6 +914,9 @@ class RocheODEReal(nn.Module):
         options = dict(options)
         theta = torch.stack([self.k_immunity, self.kel, self.kel2])
         dose = self.dosage[..., 0] if self.dosage.shape[-1] == 1 else self.dosage.sum(-1)
+        if self.dose_grad and dose.requires_grad and torch.is_grad_enabled():
+            raise hode.HodeConfigError("hode: RocheODEReal.dose_grad serves the chained solve (a 2-D init); the one-step-ahead "
+                                       "solve (a 3-D init) has no dose-table gradient -- detach the action or switch dose_grad off")
         return real_step.real_step_solve(init, theta, self.flat_weights(), t, dose, self.hidden_dim, method=method,
                                          perturb=bool(options.pop("perturb", False)), step_size=options.pop("step_size", None))
 
