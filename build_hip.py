@@ -67,26 +67,12 @@ def _roche_dims_units():
         [("hode_roche_dims_dp_d%d" % n, os.path.join(d, "hode_roche_dims_dp_dim.hip"), ["-DHODE_DIM=%d" % n]) for n in ROCHE_DIMS]
 
 
-def _real_dims_units():
-    d = os.path.join(CSRC, "real_dims")
-    # -Wno-unused-function: hode_rk_host.hpp is included for the partial fold; its Roche argument helpers are not called here
-    return [("hode_real_dims", os.path.join(d, "hode_real_dims.hip"), ["-Wno-unused-function"])] + \
-        [("hode_real_dims_ht%d" % n, os.path.join(d, "hode_real_dims_ht.hip"), ["-DHODE_REAL_DIMS_HT=%d" % n]) for n in REAL_DIMS_HTS]
-
-
 def _lstm_seq_units():
     # libhode.so's LSTM units compiled for this library (its checks, geometry, packing and launch code, once)
     seq = ["-DHODE_LSTM_SEQ_UNIT"]
     return [("hode_lstm_seq", os.path.join(CSRC, "lstm_seq", "hode_lstm_seq.hip"), []),
             ("hode_lstm_seq_host", os.path.join(CSRC, "hode_lstm.hip"), seq)] + \
         [("hode_lstm_seq_tpw%d" % n, os.path.join(CSRC, "hode_lstm_tpw.hip"), seq + ["-DHODE_LSTM_TPW=%d" % n]) for n in LSTM_TPWS]
-
-
-def _real_step_units():
-    d = os.path.join(CSRC, "real_step")
-    # -Wno-unused-function: hode_rk_host.hpp is included for the partial fold; its Roche argument helpers are not called here
-    return [("hode_real_step", os.path.join(d, "hode_real_step.hip"), ["-Wno-unused-function"])] + \
-        [("hode_real_step_ht%d" % n, os.path.join(d, "hode_real_step_ht.hip"), ["-DHODE_REAL_STEP_HT=%d" % n]) for n in REAL_STEP_HTS]
 
 
 def _dose_units():
@@ -101,13 +87,6 @@ def _dopri5_pp_units():
     # -Wno-unused-function: hode_rk_host.hpp is included for the partial fold; its Roche argument helpers are not called here
     return [("hode_dopri5_pp", os.path.join(d, "hode_dopri5_pp.hip"), ["-Wno-unused-function"])] + \
         [("hode_dopri5_pp_d%d" % n, os.path.join(d, "hode_dopri5_pp_dim.hip"), ["-DHODE_DIM=%d" % n]) for n in DP_DIMS]
-
-
-def _real_dose_units():
-    d = os.path.join(CSRC, "real_dose")
-    # -Wno-unused-function: hode_rk_host.hpp is included for the partial fold; its Roche argument helpers are not called here
-    return [("hode_real_dose", os.path.join(d, "hode_real_dose.hip"), ["-Wno-unused-function"])] + \
-        [("hode_real_dose_ht%d" % n, os.path.join(d, "hode_real_dose_ht.hip"), ["-DHODE_REAL_DOSE_HT=%d" % n]) for n in REAL_DOSE_HTS]
 
 
 class Library:
@@ -133,6 +112,18 @@ def _multi(name, units):
     return Library("libhode_%s.so" % name, PKG + "/csrc/" + name, "include/hode_%s.h" % name, units)
 
 
+def _real_side(name, hts):
+    """A side library of the real-data hybrid rhs (csrc/hode_real_side_host.hpp): csrc/<name>/ with the entry points in
+    hode_<name>.hip and hode_<name>_ht.hip compiled once per hidden-tile count of `hts`."""
+    d = os.path.join(CSRC, name)
+
+    def units():
+        # -Wno-unused-function: hode_rk_host.hpp is included for the partial fold; its Roche argument helpers are not called here
+        return [("hode_" + name, os.path.join(d, "hode_%s.hip" % name), ["-Wno-unused-function"])] + \
+            [("hode_%s_ht%d" % (name, n), os.path.join(d, "hode_%s_ht.hip" % name), ["-DHODE_%s_HT=%d" % (name.upper(), n)]) for n in hts]
+    return _multi(name, units)
+
+
 #: every library, by file name, in build order
 LIBRARIES = {lib.name: lib for lib in (
     Library("libhode.so", PKG + "/csrc", "include/hode.h", units),  # the solvers, the LSTM, the readouts and the metrics
@@ -143,9 +134,9 @@ LIBRARIES = {lib.name: lib for lib in (
     _side("probe"),                           # test only: the shared device helpers on their own; nothing under hode/ loads it
     _multi("neural_odd", _neural_odd_units),  # the NeuralODE kernels at the odd latent sizes 5 .. 15, a unit per size
     _multi("roche_dims", _roche_dims_units),  # the hybrid Roche kernels at ROCHE_DIMS, a fixed-grid and a dopri5 unit per size
-    _multi("real_dims", _real_dims_units),    # the real-data hybrid rhs at the latent sizes 5 .. 20, a unit per hidden-tile count
+    _real_side("real_dims", REAL_DIMS_HTS),   # the real-data hybrid rhs at the latent sizes 5 .. 20, a unit per hidden-tile count
     _multi("lstm_seq", _lstm_seq_units),      # the LSTM kernels with the hidden state of every step: libhode.so's units again
-    _multi("real_step", _real_step_units),    # the one-step-ahead solve of the real-data hybrid rhs, a unit per hidden-tile count
+    _real_side("real_step", REAL_STEP_HTS),   # the one-step-ahead solve of the real-data hybrid rhs, a unit per hidden-tile count
     _side("sylvester"),                       # the chain of Sylvester flows (flow.Sylvester, flow.sylvester_chain)
     _side("snf"),                             # the Sylvester-flow posterior with its Monte-Carlo KL (EncoderSylvesterLSTM)
     _multi("dopri5_pp", _dopri5_pp_units),    # dopri5 of the hybrid Roche rhs with per-patient step control, a unit per DP_DIMS
@@ -158,7 +149,7 @@ MORE_LIBRARIES = {lib.name: lib for lib in (
 
 #: libraries beside both (all_libraries() is pinned by tests/test_dose_host.py), built, linked and stamped with them
 LATER_LIBRARIES = {lib.name: lib for lib in (
-    _multi("real_dose", _real_dose_units),    # the adjoint of the real-data hybrid rhs with dose-table gradients, a unit per hidden-tile count
+    _real_side("real_dose", REAL_DOSE_HTS),   # the adjoint of the real-data hybrid rhs with dose-table gradients, a unit per hidden-tile count
 )}
 
 

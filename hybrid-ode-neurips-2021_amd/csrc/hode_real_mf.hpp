@@ -459,8 +459,15 @@ constexpr float kRealThird = (float)(1.0 / 3.0);
 // RealTileRagged (runtime M <= 16: rows >= M are zero and stay zero -- u = tanh(0) = 0, dH = (1 - z)(u - H) = 0 -- and every
 // load and store of a state row is element-wise and guarded, so that nothing outside the D floats of a patient is touched).
 // `lds` is the RealGradAcc image of the on-chip backward (RealGradAcc<HT>::kLdsFloats floats; unused otherwise).
-template <int HT, int METHOD, bool BWD, bool ONCHIP, class Tile>
-HODE_DEV void real_mf_body(const RealArgs& a, const Tile tile, float* lds) {
+// `dose` is the on-chip backward's hook for the gradient of the dose table (real_dose/hode_real_dose_ht.hip).  A hook with
+// kGrad set is called before the sweep (begin), after the acc.add of every stage VJP (tap) and after the sweep, before
+// grad_y0 is stored (finish); this one does nothing, and the kernels without a hook compile as if there were none.
+struct NoRealDoseGrad {
+  static constexpr bool kGrad = false;
+};
+template <int HT, int METHOD, bool BWD, bool ONCHIP, class Tile, class DOSE = NoRealDoseGrad>
+HODE_DEV void real_mf_body(const RealArgs& a, const Tile tile, float* lds, DOSE dose = DOSE{}) {
+  static_assert(!DOSE::kGrad || (BWD && ONCHIP), "the dose hook is the on-chip backward's");
   typedef RealMf<HT, Tile> Net;
   typedef typename Net::Stage Stage;
   constexpr int NT2 = 2 * HT;
@@ -504,6 +511,7 @@ HODE_DEV void real_mf_body(const RealArgs& a, const Tile tile, float* lds) {
     v4 lamX, lamH;
     load_state(a.grad_h + (size_t)(a.T - 1) * row + (size_t)p * D, lamX, lamH);
     lamX = lv * lamX; lamH = lv * lamH;
+    if constexpr (DOSE::kGrad) dose.begin(a, p, g0 && live, nn.kel);
 
     auto tape_tile = [&](float* tp, int first_row, int nrows, const v4& v) {  // rows 4g + r of a 16-row vector
       if (!live) return;
@@ -538,6 +546,7 @@ HODE_DEV void real_mf_body(const RealArgs& a, const Tile tile, float* lds) {
         nn.vjp(s[q], gX, gH, aX, aH, U1, u12, u22, ur, uz, uh, dth);
         if constexpr (ONCHIP) {
           acc.add(U1, s[q].ah, s[q].X, u12, u22, uh, uz, ur, s[q].RH, s[q].Hs, g, nn.n);
+          if constexpr (DOSE::kGrad) dose.tap(st, q, gX[3]);
           return;
         }
         float* tp = tp0 + (size_t)q * tstride;
@@ -561,6 +570,7 @@ HODE_DEV void real_mf_body(const RealArgs& a, const Tile tile, float* lds) {
       load_state(a.grad_h + (size_t)n * row + (size_t)p * D, ghX, ghH);
       lamX = lamX + lv * ghX; lamH = lamH + lv * ghH;
     }
+    if constexpr (DOSE::kGrad) dose.finish();
     store_state(a.grad_y0 + (size_t)p * D, lamX, lamH);
     // only lanes g == 0 of live patients carry scalar-gradient terms (X, gX are zero elsewhere; lv zeroes dead patients)
 #pragma unroll

@@ -1,11 +1,12 @@
 // Internal to libhode_real_dims.so: what the per-hidden-tile units (hode_real_dims_ht.hip, compiled once per
-// -DHODE_REAL_DIMS_HT=<1 .. 4>) give the entry points (hode_real_dims.hip).
+// -DHODE_REAL_DIMS_HT=<1 .. 4>, the HODE_REAL_SIDE_HTS of ../hode_real_side_host.hpp) give the entry points
+// (hode_real_dims.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 #include "../../../include/hode_real_dims.h"
-#include "../hode_host.hpp"
+#include "../hode_real_side_host.hpp"
 
 namespace hode {
 
@@ -14,17 +15,11 @@ constexpr int kRealDimsMinLatent = 5, kRealDimsMaxLatent = 20, kRealDimsMaxHidde
 #define HODE_REAL_DIMS_TEXT "latent_dim 5 .. 20 with hidden_dim 1 .. 64"
 #define HODE_REAL_DIMS_LIBHODE_TEXT "libhode.so has latent_dim 4 and 20"
 
-struct RealArgs;
-
 // Launch real_dims_kernel<HT, method, bwd> over ceil(B / 16) waves and, after a backward, real_dims_fold_kernel<HT> into
 // the flat weight gradient `grad_w`.  `M` = latent_dim - 4.  One definition per unit.
-#define HODE_REAL_DIMS_HTS(X) X(1) X(2) X(3) X(4)
 #define HODE_REAL_DIMS_DECL(n) \
   int real_dims_launch_ht##n(int method, bool bwd, const RealArgs& a, int M, float* grad_w, hipStream_t s);
-HODE_REAL_DIMS_HTS(HODE_REAL_DIMS_DECL)
+HODE_REAL_SIDE_HTS(HODE_REAL_DIMS_DECL)
 #undef HODE_REAL_DIMS_DECL
-
-// floats of one wave's block of weight-gradient partials (RealGradAcc<HT>::NP; the units assert the equality)
-constexpr size_t real_dims_partial_floats(int ht) { return (size_t)(4 * ht + 3) * 256 + 16; }
 
 }  // namespace hode

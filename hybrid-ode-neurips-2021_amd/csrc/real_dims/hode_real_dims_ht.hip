@@ -16,7 +16,7 @@ namespace hode {
 
 constexpr int kHT = HODE_REAL_DIMS_HT;
 static_assert(kHT >= 1 && kHT <= 4, "hidden tiles");
-static_assert(RealGradAcc<kHT>::NP == real_dims_partial_floats(kHT), "partial block size");
+static_assert(RealGradAcc<kHT>::NP == real_side_partial_floats(kHT), "partial block size");
 
 template <int HT, int METHOD, bool BWD>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void real_dims_kernel(RealArgs a, int M) {
@@ -37,10 +37,7 @@ static void launch_method(bool bwd, const RealArgs& a, int M, dim3 grid, hipStre
   else hipLaunchKernelGGL((real_dims_kernel<kHT, METHOD, false>), grid, dim3(64), 0, s, a, M);
 }
 
-#define HODE_REAL_DIMS_CAT2(a, b) a##b
-#define HODE_REAL_DIMS_CAT(a, b) HODE_REAL_DIMS_CAT2(a, b)
-int HODE_REAL_DIMS_CAT(real_dims_launch_ht, HODE_REAL_DIMS_HT)(int method, bool bwd, const RealArgs& a, int M, float* grad_w,
-                                                               hipStream_t s) {
+int HODE_CAT(real_dims_launch_ht, HODE_REAL_DIMS_HT)(int method, bool bwd, const RealArgs& a, int M, float* grad_w, hipStream_t s) {
   const dim3 grid((a.B + 15) / 16);
   switch (method) {
     case HODE_METHOD_EULER: launch_method<HODE_METHOD_EULER>(bwd, a, M, grid, s); break;

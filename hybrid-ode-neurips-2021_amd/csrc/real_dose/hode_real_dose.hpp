@@ -1,11 +1,12 @@
 // Internal to libhode_real_dose.so: what the per-hidden-tile units (hode_real_dose_ht.hip, compiled once per
-// -DHODE_REAL_DOSE_HT=<1 .. 4>) give the entry points (hode_real_dose.hip).
+// -DHODE_REAL_DOSE_HT=<1 .. 4>, the HODE_REAL_SIDE_HTS of ../hode_real_side_host.hpp) give the entry points
+// (hode_real_dose.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 #include "../../../include/hode_real_dose.h"
-#include "../hode_host.hpp"
+#include "../hode_real_side_host.hpp"
 
 namespace hode {
 
@@ -13,17 +14,11 @@ namespace hode {
 constexpr int kRealDoseMinLatent = 5, kRealDoseMaxLatent = 20, kRealDoseMaxHidden = 64;
 #define HODE_REAL_DOSE_TEXT "latent_dim 5 .. 20 with hidden_dim 1 .. 64, methods euler / midpoint / rk4"
 
-struct RealArgs;
-
 // Launch real_dose_bwd_kernel<HT, method> over ceil(B / 16) waves and real_dose_fold_kernel<HT> into the flat weight
 // gradient `grad_w`.  `M` = latent_dim - 4; `grad_act` is the [Ta][B] output.  One definition per unit.
-#define HODE_REAL_DOSE_HTS(X) X(1) X(2) X(3) X(4)
 #define HODE_REAL_DOSE_DECL(n) \
   int real_dose_launch_ht##n(int method, const RealArgs& a, int M, float* grad_act, float* grad_w, hipStream_t s);
-HODE_REAL_DOSE_HTS(HODE_REAL_DOSE_DECL)
+HODE_REAL_SIDE_HTS(HODE_REAL_DOSE_DECL)
 #undef HODE_REAL_DOSE_DECL
-
-// floats of one wave's block of weight-gradient partials (RealGradAcc<HT>::NP; the units assert the equality)
-constexpr size_t real_dose_partial_floats(int ht) { return (size_t)(4 * ht + 3) * 256 + 16; }
 
 }  // namespace hode

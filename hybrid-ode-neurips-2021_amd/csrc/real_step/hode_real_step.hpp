@@ -1,11 +1,12 @@
 // Internal to libhode_real_step.so: what the per-hidden-tile units (hode_real_step_ht.hip, compiled once per
-// -DHODE_REAL_STEP_HT=<1 .. 4>) give the entry points (hode_real_step.hip).
+// -DHODE_REAL_STEP_HT=<1 .. 4>, the HODE_REAL_SIDE_HTS of ../hode_real_side_host.hpp) give the entry points
+// (hode_real_step.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 #include "../../../include/hode_real_step.h"
-#include "../hode_host.hpp"
+#include "../hode_real_side_host.hpp"
 
 namespace hode {
 
@@ -18,8 +19,6 @@ constexpr int kRealStepMinLatent = 5, kRealStepMaxLatent = 20, kRealStepMaxHidde
 // fixed cost of a wave in units of one interval's work (DESIGN.md 4.6c holds the measurement behind the number)
 constexpr long kRealStepSimds = 1024, kRealStepWaveCost = 2;
 
-struct RealArgs;
-
 // how the N intervals are cut into runs: wave (x, y) owns patients 16 x .. 16 x + 15 and the intervals y C .. y C + C - 1
 struct RealStepGeom {
   int N, S, C;
@@ -28,13 +27,9 @@ struct RealStepGeom {
 
 // Launch real_step_kernel<HT, method, bwd> over ceil(B / 16) x ceil(N / C) waves and, after a backward,
 // real_step_fold_kernel<HT> into the flat weight gradient `grad_w`.  `M` = latent_dim - 4.  One definition per unit.
-#define HODE_REAL_STEP_HTS(X) X(1) X(2) X(3) X(4)
 #define HODE_REAL_STEP_DECL(n) \
   int real_step_launch_ht##n(int method, bool bwd, const RealArgs& a, const RealStepGeom& geo, int M, float* grad_w, hipStream_t s);
-HODE_REAL_STEP_HTS(HODE_REAL_STEP_DECL)
+HODE_REAL_SIDE_HTS(HODE_REAL_STEP_DECL)
 #undef HODE_REAL_STEP_DECL
-
-// floats of one wave's block of weight-gradient partials (RealGradAcc<HT>::NP; the units assert the equality)
-constexpr size_t real_step_partial_floats(int ht) { return (size_t)(4 * ht + 3) * 256 + 16; }
 
 }  // namespace hode

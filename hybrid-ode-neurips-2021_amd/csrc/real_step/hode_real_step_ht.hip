@@ -18,7 +18,7 @@ namespace hode {
 
 constexpr int kHT = HODE_REAL_STEP_HT;
 static_assert(kHT >= 1 && kHT <= 4, "hidden tiles");
-static_assert(RealGradAcc<kHT>::NP == real_step_partial_floats(kHT), "partial block size");
+static_assert(RealGradAcc<kHT>::NP == real_side_partial_floats(kHT), "partial block size");
 
 // a.y0 [N][B][D] start states, a.t [N][S + 1], a.h / a.grad_h [N + 1][B][D], a.grad_y0 [N][B][D]; a.T is not read.
 // Every load and store of a state row is element-wise and guarded (real_load_state / real_store_state of the ragged
@@ -131,10 +131,8 @@ static void launch_method(bool bwd, const RealArgs& a, const RealStepGeom& geo, 
   else hipLaunchKernelGGL((real_step_kernel<kHT, METHOD, false>), grid, dim3(64), 0, s, a, geo, M);
 }
 
-#define HODE_REAL_STEP_CAT2(a, b) a##b
-#define HODE_REAL_STEP_CAT(a, b) HODE_REAL_STEP_CAT2(a, b)
-int HODE_REAL_STEP_CAT(real_step_launch_ht, HODE_REAL_STEP_HT)(int method, bool bwd, const RealArgs& a, const RealStepGeom& geo,
-                                                               int M, float* grad_w, hipStream_t s) {
+int HODE_CAT(real_step_launch_ht, HODE_REAL_STEP_HT)(int method, bool bwd, const RealArgs& a, const RealStepGeom& geo, int M,
+                                                    float* grad_w, hipStream_t s) {
   const dim3 grid((a.B + 15) / 16, (geo.N + geo.C - 1) / geo.C);
   switch (method) {
     case HODE_METHOD_EULER: launch_method<HODE_METHOD_EULER>(bwd, a, geo, M, grid, s); break;

@@ -51,7 +51,9 @@ def test_sizes_agree_everywhere():
     internal = open(os.path.join(build_hip.CSRC, "real_dims", "hode_real_dims.hpp")).read()
     assert "constexpr int kRealDimsMinLatent = 5, kRealDimsMaxLatent = 20, kRealDimsMaxHidden = 64;" in internal
     assert '#define HODE_REAL_DIMS_TEXT "%s"\n' % SIZES.decode() in internal
-    assert "#define HODE_REAL_DIMS_HTS(X) " + " ".join("X(%d)" % n for n in cases.HTS) + "\n" in internal
+    side = open(os.path.join(build_hip.CSRC, "hode_real_side_host.hpp")).read()   # the hidden-tile counts: once, for the three side libraries
+    assert "#define HODE_REAL_SIDE_HTS(X) " + " ".join("X(%d)" % n for n in cases.HTS) + "\n" in side
+    assert "HODE_REAL_SIDE_HTS(HODE_REAL_DIMS_DECL)" in internal and "HODE_REAL_DIMS_HTS" not in internal
     # libhode.so's own sizes for this rhs, as its check states them
     assert RD.LIBHODE_DIMS == (4, 20)
     assert "(have 4, 20)" in open(os.path.join(build_hip.CSRC, "hode_real.hip")).read()
@@ -65,6 +67,9 @@ def test_the_row_of_the_build_table():
     want = ["hode_real_dims"] + ["hode_real_dims_ht%d" % n for n in cases.HTS]
     assert sorted(n for n, _, _ in row.units()) == sorted(want)
     assert build_hip.PKG + "/csrc/hode_real_mf.hpp" in hashed and build_hip.PKG + "/csrc/hode_rk_host.hpp" in hashed
+    assert build_hip.PKG + "/csrc/hode_real_side_host.hpp" in hashed
+    host = open(os.path.join(build_hip.CSRC, "real_dims", "hode_real_dims.hip")).read()
+    assert "hode_error_state.hpp" in host and "__global__" not in host   # entry points only; the checks and the layout are the shared header's
     # libhode.so keeps its own unit of the shared device code
     assert "hode_real_mf" in [n for n, _, _ in build_hip.LIBRARIES["libhode.so"].units()]
 

@@ -87,22 +87,38 @@ def test_the_row_is_in_the_third_table_and_the_first_two_are_as_they_were():
 
 
 def test_the_device_code_is_compiled_not_copied():
-    """The reverse time loop is this directory's; the rhs, its VJP, the accumulator, its fold, the state I/O, the dose and the
-    two step macros are hode_real_mf.hpp's, compiled again and not restated."""
+    """The dose hook is this directory's; the reverse time loop with the rhs, its VJP, the accumulator, the state I/O, the
+    dose and the two step macros is hode_real_mf.hpp's real_mf_body, compiled again with the hook and not restated."""
     src = open(os.path.join(build_hip.CSRC, "real_dose", "hode_real_dose_ht.hip")).read()
-    for name in ("RealMf<HT, RealTileRagged>", "RealGradAcc<HT>", "real_grad_fold<HT>", "real_load_state(", "real_store_state(",
-                 "real_set_dose(", "real_dose_table(", "HODE_REAL_STEP_STAGES(", "HODE_REAL_STEP_CHAIN(", "nn.vjp(", "acc.add(",
+    for name in ("real_mf_body<HT, METHOD, true, true>(a, RealTileRagged{M}, lds, RealDoseGrad{grad_act})", "RealGradAcc<HT>",
+                 "real_grad_fold<HT>", "static constexpr bool kGrad = true;",
                  "__launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))", '#include "../hode_real_mf.hpp"'):
         assert name in src, name
+    for restated in ("HODE_REAL_STEP_STAGES(", "HODE_REAL_STEP_CHAIN(", "nn.vjp(", "acc.add(", "real_load_state(", "real_store_state(",
+                     "real_set_dose(", "real_dose_table(", "RealMf<", "wave_sum(", "a.partials", "acc.store("):
+        assert restated not in src, restated
+    assert not re.search(r"for\s*\([^)]*a\.T\b", src)   # no loop over the time grid
+    shared = open(os.path.join(build_hip.CSRC, "hode_real_mf.hpp")).read()
+    body = shared[shared.index("void real_mf_body("):]
+    for name in ("RealMf<HT, Tile>", "real_load_state(", "real_store_state(", "real_set_dose(", "real_dose_table(", "HODE_REAL_STEP_STAGES(",
+                 "HODE_REAL_STEP_CHAIN(", "nn.vjp(", "acc.add(", "for (int n = a.T - 2; n >= 0; --n)"):
+        assert name in body, name
+    # the hook's three calls, compiled out of every kernel without one
+    assert body.count("if constexpr (DOSE::kGrad) dose.") == 3 and "static constexpr bool kGrad = false;" in shared
+    for call in ("dose.begin(a, p, g0 && live, nn.kel);", "dose.tap(st, q, gX[3]);", "dose.finish();"):
+        assert body.count(call) == 1, call
+    assert body.index("acc.add(") < body.index("dose.tap(") < body.index("dose.finish()") < body.index("store_state(a.grad_y0")
     for definition in ("struct RealMf", "struct RealGradAcc", "HODE_DEV void real_grad_fold", "HODE_DEV void real_load_state",
                        "HODE_DEV void real_store_state", "HODE_DEV void real_set_dose", "#define HODE_REAL_STEP", "mfma4(",
                        "struct RStageTimes", "HODE_DEV void real_dose_table", "0.375f", "kRealThird", "atomic"):
         assert definition not in src, definition
     host = open(os.path.join(build_hip.CSRC, "real_dose", "hode_real_dose.hip")).read()
-    assert "launch_fold_partials(" in host and "hode_error_state.hpp" in host and "__global__" not in host
+    assert "hode_error_state.hpp" in host and "__global__" not in host
+    side = open(os.path.join(build_hip.CSRC, "hode_real_side_host.hpp")).read()   # the checks, the layout and the dispatch of the three real_* libraries
+    assert "real_side_launch(" in host and "launch_fold_partials(" in side and "__global__" not in side
     files = build_hip.digest_files(LIB)
     for f in ("hode_real_mf.hpp", "hode_real_args.hpp", "hode_common.hpp", "hode_rk_host.hpp", "hode_error_state.hpp", "hode_host.hpp",
-              "real_dose/hode_real_dose.hpp", "real_dose/hode_real_dose_ht.hip", "real_dose/hode_real_dose.hip"):
+              "hode_real_side_host.hpp", "real_dose/hode_real_dose.hpp", "real_dose/hode_real_dose_ht.hip", "real_dose/hode_real_dose.hip"):
         assert build_hip.PKG + "/csrc/" + f in files, f
     assert "include/hode_real_dose.h" in files and "include/hode.h" in files
 

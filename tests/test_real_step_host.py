@@ -48,7 +48,9 @@ def test_sizes_agree_everywhere():
     internal = open(os.path.join(build_hip.CSRC, "real_step", "hode_real_step.hpp")).read()
     assert "constexpr int kRealStepMinLatent = 5, kRealStepMaxLatent = 20, kRealStepMaxHidden = 64, kRealStepMaxSub = 8;" in internal
     assert '#define HODE_REAL_STEP_TEXT "%s"\n' % SIZES.decode() in internal
-    assert "#define HODE_REAL_STEP_HTS(X) " + " ".join("X(%d)" % n for n in cases.HTS) + "\n" in internal
+    side = open(os.path.join(build_hip.CSRC, "hode_real_side_host.hpp")).read()   # the hidden-tile counts: once, for the three side libraries
+    assert "#define HODE_REAL_SIDE_HTS(X) " + " ".join("X(%d)" % n for n in cases.HTS) + "\n" in side
+    assert "HODE_REAL_SIDE_HTS(HODE_REAL_STEP_DECL)" in internal and "HODE_REAL_STEP_HTS" not in internal
     assert "5 .. 20" in RS.sizes_text() and "1 .. 64" in RS.sizes_text() and "1 .. 8" in RS.sizes_text()
 
 
@@ -60,6 +62,9 @@ def test_the_row_of_the_build_table():
     want = ["hode_real_step"] + ["hode_real_step_ht%d" % n for n in cases.HTS]
     assert sorted(n for n, _, _ in row.units()) == sorted(want)
     assert build_hip.PKG + "/csrc/hode_real_mf.hpp" in hashed and build_hip.PKG + "/csrc/hode_rk_host.hpp" in hashed
+    assert build_hip.PKG + "/csrc/hode_real_side_host.hpp" in hashed
+    host = open(os.path.join(build_hip.CSRC, "real_step", "hode_real_step.hip")).read()
+    assert "hode_error_state.hpp" in host and host.count("__global__") == 1 and "void real_step_dose_kernel(" in host   # the dose-table prelude alone
 
 
 def test_the_device_code_is_shared_not_copied():

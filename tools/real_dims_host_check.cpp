@@ -1,5 +1,6 @@
 // Stand-alone walk through the host code of libhode_real_dims.so -- the domain check, the workspace layout and the
-// dispatch of csrc/real_dims/hode_real_dims.hip -- with no GPU and no launch: every call here is refused before the
+// dispatch of csrc/real_dims/hode_real_dims.hip, most of it csrc/hode_real_side_host.hpp, which the other two real_*
+// side libraries share -- with no GPU and no launch: every call here is refused before the
 // dispatch, and the per-hidden-tile launchers are replaced by stubs that abort if one is reached.  Meant for a sanitizer
 // build of the host side (from the repository root):
 //   hipcc --offload-arch=gfx950 -std=c++17 -g -O1 -Xarch_host -fsanitize=address,undefined -fsanitize=address,undefined \
@@ -18,7 +19,7 @@ namespace hode {
     fprintf(stderr, "real_dims_host_check: the dispatch reached a launch (ht%d)\n", n);          \
     abort();                                                                                     \
   }
-HODE_REAL_DIMS_HTS(HODE_REAL_DIMS_STUB)
+HODE_REAL_SIDE_HTS(HODE_REAL_DIMS_STUB)
 #undef HODE_REAL_DIMS_STUB
 }  // namespace hode
 
