@@ -2,8 +2,8 @@
 """Build the gfx950 kernel libraries in-tree with hipcc: `python build_hip.py [-j N] [--force]`.
 
 LIBRARIES has one row per library: its file name in hode/, the directory of its sources, its C ABI header and its compile
-units; MORE_LIBRARIES and LATER_LIBRARIES hold further rows of the same type, and library(name) looks a row up in all three.
-build() compiles the units of every row (every_library()) in one thread pool (a unit is recompiled when a file of its depfile, its flags
+units; MORE_LIBRARIES, LATER_LIBRARIES and PATIENT_LIBRARIES hold further rows of the same type, and library(name) looks a row up in all four.
+build() compiles the units of every row (built_libraries()) in one thread pool (a unit is recompiled when a file of its depfile, its flags
 or this script changed), links each library whose objects are newer than it, and writes digest(<library>) next to it as
 <library>.so.digest; tests and hode/_loader.py compare that stamp with the tree.  The digest covers the header, every source
 of the row's directory, the units' sources and everything they include from inside the tree, the flags and the units."""
@@ -30,6 +30,7 @@ ROCHE_DIMS = (5, 7, 9, 10, 11, 13, 14, 15, 16)  # csrc/roche_dims/: the hybrid d
 REAL_DIMS_HTS = (1, 2, 3, 4)  # csrc/real_dims/hode_real_dims_ht.hip: hidden tiles of 16 (hidden_dim 1 .. 64)
 REAL_STEP_HTS = (1, 2, 3, 4)  # csrc/real_step/hode_real_step_ht.hip: the same tiles for the one-step-ahead solve
 REAL_DOSE_HTS = (1, 2, 3, 4)  # csrc/real_dose/hode_real_dose_ht.hip: the same tiles for the adjoint with dose-table gradients
+REAL_PP_HTS = (1, 2, 3, 4)  # csrc/real_pp/hode_real_pp_ht.hip: the same tiles for dopri5 with per-patient step control
 LSTM_TPWS = (1, 2, 3, 4, 5, 6, 8, 10)   # padded hidden sizes 16 * TPW (csrc/hode_lstm_tpw.hip)
 # per-unit flags (measured on MI355X)
 # -fno-slp-vectorize on the split kernels: packed-fp32 pairing costs more v_mov than it saves (step 0.228 -> 0.207 ms)
@@ -153,12 +154,18 @@ LATER_LIBRARIES = {lib.name: lib for lib in (
 )}
 
 
+#: libraries beside all three (every_library() is pinned by tests/test_real_dose_host.py), built, linked and stamped with them
+PATIENT_LIBRARIES = {lib.name: lib for lib in (
+    _real_side("real_pp", REAL_PP_HTS),       # dopri5 of the real-data hybrid rhs with per-patient step control, a unit per hidden-tile count
+)}
+
+
 def library(name):
-    """The row of `name`, from LIBRARIES, MORE_LIBRARIES or LATER_LIBRARIES."""
-    for table in (LIBRARIES, MORE_LIBRARIES):
+    """The row of `name`, from LIBRARIES, MORE_LIBRARIES, LATER_LIBRARIES or PATIENT_LIBRARIES."""
+    for table in (LIBRARIES, MORE_LIBRARIES, LATER_LIBRARIES):
         if name in table:
             return table[name]
-    return LATER_LIBRARIES[name]
+    return PATIENT_LIBRARIES[name]
 
 
 def all_libraries():
@@ -167,8 +174,13 @@ def all_libraries():
 
 
 def every_library():
-    """Every row of all three tables, in build order: what build() compiles, links and stamps."""
+    """Every row of the first three tables, in build order."""
     return all_libraries() + list(LATER_LIBRARIES.values())
+
+
+def built_libraries():
+    """Every row of all four tables, in build order: what build() compiles, links and stamps."""
+    return every_library() + list(PATIENT_LIBRARIES.values())
 
 
 OUT = LIBRARIES["libhode.so"].out
@@ -270,7 +282,7 @@ def link(out, objs):
 def build(jobs=7, force=False, verbose=True):
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
         futs = []
-        for lib in every_library():
+        for lib in built_libraries():
             os.makedirs(lib.obj, exist_ok=True)
             futs += [ex.submit(compile_one, n, s, e, force, lib.obj) for n, s, e in lib.units()]
         for f in futs:
@@ -279,7 +291,7 @@ def build(jobs=7, force=False, verbose=True):
                 print("  hipcc %-14s %.1fs" % (name, dt), flush=True)
             if verbose and err.strip():
                 print(err[-2000:], file=sys.stderr)
-    for lib in every_library():
+    for lib in built_libraries():
         objs = [os.path.join(lib.obj, n + ".o") for n, _, _ in lib.units()]
         if force or not os.path.exists(lib.out) or os.path.getmtime(lib.out) < max(os.path.getmtime(o) for o in objs):
             link(lib.out, objs)

@@ -788,6 +788,34 @@ class _RocheRealDoseGrad(torch.autograd.Function):
         return gy0, gth, gw, None, gact, None, None, None
 
 
+class _RocheRealPatientDopri5(torch.autograd.Function):
+    """h = odeint(RocheODEReal, y0, t, method="dopri5", options={"step_t": t}) with per-patient step control: the two
+    launches of ``hode.real_pp`` (libhode_real_pp.so).  Gradients for y0, theta and wflat; none for t and the dose table
+    (their .grad stays None).  Every step size is a constant in the backward, dt_0 included."""
+
+    @staticmethod
+    def forward(ctx, y0, theta, wflat, t, act, hidden, rtol, atol, grad_enabled=True):
+        from hode import real_pp
+        f32c = hode.solver._f32c
+        y0c, thc, wc, tc, ac = f32c(y0), f32c(theta), f32c(wflat), f32c(t), f32c(act)
+        # `needs_input_grad` reflects requires_grad, not the grad mode, and inside forward() grad mode is always off: the
+        # caller samples it before .apply().  Nothing to differentiate: no tape at all.
+        no_tape = not (grad_enabled and any(ctx.needs_input_grad[:3]))
+        h, ws, stats = real_pp.real_patient_dopri5_forward(y0c, thc, wc, tc, ac, hidden, rtol=rtol, atol=atol, no_tape=no_tape)
+        ctx.save_for_backward(h, thc, wc, tc, ac, y0c, ws, stats["n_accepted"])
+        ctx.meta = (int(hidden), float(rtol), float(atol), int(stats["max_steps"]))
+        return h
+
+    @staticmethod
+    def backward(ctx, grad_h):
+        from hode import real_pp
+        h, thc, wc, tc, ac, y0c, ws, n_accepted = ctx.saved_tensors
+        hidden, rtol, atol, steps = ctx.meta
+        gy0, gth, gw = real_pp.real_patient_dopri5_backward(y0c, thc, wc, tc, ac, hidden, h, ws, n_accepted, steps,
+                                                            hode.solver._f32c(grad_h), rtol=rtol, atol=atol)
+        return gy0, gth, gw, None, None, None, None, None, None
+
+
 class RocheODEReal(nn.Module):
     """Real-data hybrid rhs: two small MLPs for x1, x2, expert x3 / Dose2, GRU-ODE block on the rest (model.py:570-657).
 
@@ -821,6 +849,9 @@ class RocheODEReal(nn.Module):
         # fixed-grid methods only: True lets a gradient reach the treatment -- with an action that requires grad the solve's
         # backward fills the gradient of the dose table (hode.real_dose, libhode_real_dose.so)
         self.dose_grad = False
+        # dopri5 only: "batch" has no kernel for this rhs (refused); "patient" gives every patient a controller of its own
+        # and cuts the steps at the output times (hode.real_pp); options["step_control"] of hode.odeint overrides it for one call
+        self.step_control = "batch"
         self.to(self.device)  # the reference leaves the sub-networks on the default device; everything lives on one here
 
     def set_action_static(self, action, static):
@@ -865,7 +896,10 @@ class RocheODEReal(nn.Module):
     def hode_solve(self, y0, t, rtol, atol, method, options):
         if self.dosage is None:
             raise RuntimeError("RocheODEReal: call set_action_static(a, s) before integrating")
-        _refuse_patient_step_control(self, options)
+        if _step_control(self, options) == "patient":
+            if method == "dopri5":
+                return self._solve_patient_dopri5(y0, t, rtol, atol, options)
+            _refuse_patient_step_control(self, {"step_control": "patient"})
         from hode import real
         if method == "dopri5":
             # DecoderReal hands dopri5 a `step_t` grid (model.py:826: steps are cut at the hourly dose switches); that
@@ -901,6 +935,30 @@ class RocheODEReal(nn.Module):
             lambda grid: real.real_solve(y0, theta, wflat, grid, dose, self.hidden_dim, method=method, perturb=perturb, library=None),
             t, step_size)
 
+    def _solve_patient_dopri5(self, y0, t, rtol, atol, options):
+        """dopri5 with per-patient step control and the steps cut at the output times (``hode.real_pp``): what
+        ``options["step_t"] = t`` means for a batch of one.  ``step_size`` and ``perturb`` are ignored, as torchdiffeq ignores
+        them for dopri5.  Every refusal comes before a library is loaded."""
+        from hode import real_pp
+        real_pp.check_domain(self.latent_dim, self.hidden_dim)
+        step_t = options.pop("step_t", None)
+        if step_t is not None and step_t is not t:
+            step_t = torch.as_tensor(step_t)
+            if step_t.shape != t.shape or not bool(torch.equal(step_t.to(t.device, t.dtype), t)):
+                raise hode.HodeConfigError("hode: RocheODEReal with step_control='patient' cuts the steps at the output times; "
+                                           "options['step_t'] must be the output grid t itself (or absent)")
+        options.pop("step_size", None)
+        options.pop("perturb", None)
+        dose = self.dosage[..., 0] if self.dosage.shape[-1] == 1 else self.dosage.sum(-1)
+        grad_enabled = torch.is_grad_enabled()
+        if self.dose_grad and dose.requires_grad and grad_enabled:
+            raise hode.HodeConfigError("hode: RocheODEReal.dose_grad serves the fixed-grid methods euler / midpoint / rk4; "
+                                       "method='dopri5' (step_control='patient') has no dose-table gradient -- detach the "
+                                       "action or switch dose_grad off")
+        hode.solver._require_gpu(y0, t, dose, self.kel)
+        theta = torch.stack([self.k_immunity, self.kel, self.kel2])
+        return _RocheRealPatientDopri5.apply(y0, theta, self.flat_weights(), t, dose.detach(), self.hidden_dim, float(rtol),
+                                             float(atol), grad_enabled)
 
     def hode_solve_steps(self, init, t, method, options):
         """One-step-ahead solve (reference DecoderReal.forward with a 3-D ``init``): interval i of ``t`` integrated on its
