@@ -19,8 +19,9 @@
 //     state component broadcast through op_sel, two interleaved chains per product (a packed result cannot feed the very
 //     next instruction), tanh's scale folded into the weights; the expert wave's stage / cotangent algebra on the pairs
 //     (Disease, ImmuneReact), (Immunity, Dose2);
-//   * the dose schedule is evaluated by the learned waves, stage q by quad lane q, and handed to the expert wave through a
-//     third LDS ring (4 stages in parallel instead of 4 x 9 serial instructions);
+//   * the dose schedule is handed to the expert wave through a third LDS ring: evaluated by a fifth wave on the expert
+//     wave's SIMD, below its priority, when every patient has one dose and every workgroup a CU to itself, otherwise by the
+//     learned waves, stage q by quad lane q (HODE_SPLIT_FWD_DOSE; DESIGN.md 4.3c: forward 51.3 -> 48.5 us);
 //   * HODE_FLAG_TAPE: the forward leaves the expert block's intermediate stage states in the workspace, the backward's
 //     expert wave loads them an iteration ahead instead of re-integrating (bit-identical, +16 B x 3 per patient / step);
 //     for rk4 also tanh(W Y_s + b) of the last two stages (loaded two iterations ahead by the backward's learned waves);
@@ -58,6 +59,18 @@ namespace hode {
 #ifndef HODE_SPLIT_ADJ_ONE_LINK
 #define HODE_SPLIT_ADJ_ONE_LINK 1   // rk4, learned waves: one fma between two stage VJPs, the rest beside them (sp_adjoint_step); 0: A/B
 #endif
+// Who evaluates the forward's dose schedule when every patient has one dose (the K1 body):
+//   0: the learned waves, stage q on quad lane q, handed to the expert wave through dring
+//   1: a fifth wave, one patient per lane and the four stages in turn, through the same ring; it shares the expert wave's SIMD
+//      and runs below its priority, so that it takes the issue slots the expert wave leaves.  Only while every workgroup has
+//      a CU to itself (split_method launches 320 threads then): two 4-wave workgroups share a CU at 2 waves per SIMD, two
+//      5-wave ones do not, and past one workgroup per CU that sharing is worth more (see HODE_SPLIT_WPE_FWD).
+// (The expert wave evaluating it for itself was built too: 62 more instructions per step made it the last to arrive by 250
+// cycles, forward 51.0 -> 55.9 us.)  The bodies that walk a dose table keep placement 0: a helper would load inside its loop.
+#ifndef HODE_SPLIT_FWD_DOSE
+#define HODE_SPLIT_FWD_DOSE 1
+#endif
+constexpr int kSplitFwdThreads = HODE_SPLIT_FWD_DOSE == 1 ? 320 : 256;  // the most split_fwd_kernel is launched with
 constexpr int kSplitPatients = 48;  // per workgroup: wave 0 holds all 48 (one per lane), waves 1..3 hold 16 each
 
 struct SplitArgs {
@@ -70,7 +83,7 @@ struct SplitArgs {
   const float* __restrict__ b1;
   float* __restrict__ h;
   float* __restrict__ tape;  // TAPE: [T-1][NS-1][B][4] expert stage states 1..NS-1 of every step (stage 0 is h itself)
-  unsigned long long* dbg;   // HODE_SPLIT_STAMPS builds only: [4 waves][T] s_memtime at each wave's arrival at the step barrier (block 0)
+  unsigned long long* dbg;   // HODE_SPLIT_STAMPS builds only: [5 waves][T] s_memtime at each wave's arrival at the step barrier (block 0)
   float* __restrict__ ltape; // TAPE, rk4: [T-1][B][4 quad lanes][kLearnedTapeStages * MR] learned stage derivatives (see below)
   int* __restrict__ status;
   int B, T, K, perturb;
@@ -333,8 +346,10 @@ struct MlRows {
   }
 };
 
-template <int D, int METHOD, bool ABLATE, bool HILL2, bool K1, bool TAPE>
-HODE_DEV void split_fwd_body(const SplitArgs& a) {
+template <int D, int METHOD, bool ABLATE, bool HILL2, bool K1, bool TAPE, bool DWAVE>
+HODE_DEV void split_fwd_waves(const SplitArgs& a) {
+  // DWAVE: the launch has a wave 4 and it evaluates the dose schedule, the learned waves do not (HODE_SPLIT_FWD_DOSE)
+  static_assert(K1 || !DWAVE, "the dose wave is for the one-dose body");
   constexpr int NS = sp_stages<METHOD>();
   typedef MlRows<D> Ml;
   typedef typename Ml::Own Own;
@@ -356,8 +371,36 @@ HODE_DEV void split_fwd_body(const SplitArgs& a) {
 #define HODE_FSTAMP(k)
 #endif
 
+  if (wave == 4) {
+    // ------------------------------------------------------------------ dose pipeline: one patient per lane
+    // Launched only with one dose per patient (split_method).  It keeps the learned waves' place in the hand-over: step n
+    // goes to dring[n & 1] one iteration ahead of the expert wave, behind the same barriers.  In a body that leaves the
+    // doses with the learned waves (general Hill exponents) it ends here; the barriers count the waves that are left.
+    if constexpr (DWAVE) {
+      const int slot = lane < kSplitPatients ? lane : 0;  // spare lanes: copies of slot 0, same values to the same address
+      const DoseSched<K1> ds = load_dose<K1>(a.dosage, a.dose_times, a.K, min(b0 + slot, a.B - 1));
+      auto dose_step = [&](int parity, float t0, float t1) {
+        float dose[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < NS; ++s) dose[s] = ds.at(sp_stage_time<METHOD>(t0, t1, a.perturb, s), th.kel).v;
+        *reinterpret_cast<float4*>(&dring[parity][slot][0]) = make_float4(dose[0], dose[1], dose[2], dose[3]);
+      };
+      if (a.T >= 2) dose_step(0, a.t[0], a.t[1]);  // before the first barrier: straight from global memory
+      if (a.T >= 3) dose_step(1, a.t[1], a.t[2]);
+      __builtin_amdgcn_s_waitcnt(0);  // as on the expert wave: no load of the prologue in flight at the loop head
+      __syncthreads();  // doses of steps 0 and 1 are in place; the grid is in LDS
+      __syncthreads();  // iteration 0 of the expert wave
+      for (int it = 1; it < a.T; ++it) {
+        dose_step((it + 1) & 1, tg[it + 1], tg[it + 2]);  // the expert wave is at step `it`; the grid is padded past T-1
+        HODE_FSTAMP(it)
+        __syncthreads();
+      }
+    }
+    return;
+  }
   if (wave == 0) {
     // ------------------------------------------------------------------ expert pipeline: one patient per lane
+    if constexpr (DWAVE) __builtin_amdgcn_s_setprio(3);  // ahead of the dose wave on this SIMD whenever both can issue
     const int slot = lane;
     const bool live = slot < kSplitPatients && b0 + slot < a.B;
     const int p = min(b0 + (slot < kSplitPatients ? slot : 0), a.B - 1);
@@ -373,6 +416,10 @@ HODE_DEV void split_fwd_body(const SplitArgs& a) {
       yb = pair2(v.z, v.w);
       if (live) *reinterpret_cast<float4*>(a.h + (size_t)p * D) = v;
     }
+    // Nothing the prologue loaded may still be in flight at the loop head.  The time loop only stores, and the memory counter
+    // retires in order: with the y0 load pending on the lanes that skipped the store above, the only safe wait at the first
+    // use of the state is for everything, and the loop would open every step by waiting for the stores of the step before.
+    __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();  // the learned waves' prologue fills dring for steps 0 and 1; the grid is in LDS
     auto e_iter = [&](int it, auto PAR) {
       constexpr int par = decltype(PAR)::value;  // == it & 1
@@ -432,8 +479,10 @@ HODE_DEV void split_fwd_body(const SplitArgs& a) {
     auto dose_step = [&](int parity, float t0, float t1) {  // step n goes to dring[n & 1]; lanes q >= NS: unread
       dring[parity][slot][q] = ds.at(sp_stage_time<METHOD>(t0, t1, a.perturb, q), th.kel).v;
     };
-    if (a.T >= 2) dose_step(0, a.t[0], a.t[1]);  // before the first barrier: straight from global memory
-    if (a.T >= 3) dose_step(1, a.t[1], a.t[2]);
+    if constexpr (!DWAVE) {
+      if (a.T >= 2) dose_step(0, a.t[0], a.t[1]);  // before the first barrier: straight from global memory
+      if (a.T >= 3) dose_step(1, a.t[1], a.t[2]);
+    }
     Own yo = Ml::load_own(a.y0 + (size_t)p * D, q);
     if (live) Ml::store_own(a.h + (size_t)p * D, q, yo);
     constexpr int NLT = sp_ltape_stages<METHOD>();
@@ -444,7 +493,9 @@ HODE_DEV void split_fwd_body(const SplitArgs& a) {
     auto m_iter = [&](int it, auto PAR) {
       constexpr int par = decltype(PAR)::value;  // == (it - 1) & 1 == (it + 1) & 1
       const int n = it - 1;
-      const float t_a = tg[it - 1], t_b = tg[it], t_c = tg[it + 1], t_d = tg[it + 2];  // padded past T-1
+      const float t_a = tg[it - 1], t_b = tg[it];
+      float t_c = 0.f, t_d = 0.f;
+      if constexpr (!DWAVE) { t_c = tg[it + 1]; t_d = tg[it + 2]; }  // padded past T-1
       const float dt = t_b - t_a;
       Own k[4];
       float4 e[4];  // all four expert stage states up front: one LDS round trip per step instead of one per stage
@@ -452,7 +503,7 @@ HODE_DEV void split_fwd_body(const SplitArgs& a) {
       for (int s = 0; s < NS; ++s) e[s] = *reinterpret_cast<const float4*>(&ring[par][s][slot][0]);
       __builtin_amdgcn_sched_barrier(0);  // keep the four reads here: the scheduler would sink each next to its use
       // the expert wave is at step `it` now and reads dring[it & 1]; past the last step this writes an unread slot
-      dose_step(par, t_c, t_d);
+      if constexpr (!DWAVE) dose_step(par, t_c, t_d);
 #if HODE_SPLIT_EXPERT_FIRST
       typename Ml::Part pe[4];   // bias + expert columns of every stage, ahead of the stage chain (MlRows::rhs_expert)
 #pragma unroll
@@ -485,6 +536,14 @@ HODE_DEV void split_fwd_body(const SplitArgs& a) {
       if (!vfinite(yo) && live) atomicOr(a.status, HODE_STATUS_NONFINITE);
     }
   }
+}
+
+// The body of one (HILL2, K1) pair: with one dose per patient, the pipelines with the dose wave when the launch has one.
+template <int D, int METHOD, bool ABLATE, bool HILL2, bool K1, bool TAPE>
+HODE_DEV void split_fwd_body(const SplitArgs& a) {
+  constexpr bool HAS_DWAVE = K1 && kSplitFwdThreads > 256;
+  if (HAS_DWAVE && blockDim.x > 256) split_fwd_waves<D, METHOD, ABLATE, HILL2, K1, TAPE, HAS_DWAVE>(a);
+  else split_fwd_waves<D, METHOD, ABLATE, HILL2, K1, TAPE, false>(a);
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -1225,7 +1284,8 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(HODE_SPLIT_
 }
 
 template <int D, int METHOD, bool ABLATE, bool TAPE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, HODE_SPLIT_WPE_FWD))) void split_fwd_kernel(SplitArgs a) {
+__global__ __launch_bounds__(kSplitFwdThreads) __attribute__((amdgpu_waves_per_eu(kSplitFwdThreads > 256 ? 2 : 1, HODE_SPLIT_WPE_FWD))) void split_fwd_kernel(SplitArgs a) {
+  // (a minimum below the 2 waves per SIMD that five waves imply makes the backend drop the whole attribute, the bound included)
   const bool hill2 = ABLATE || (a.theta[0] == 2.0f && a.theta[1] == 2.0f);
   if (hill2 && a.K == 1) split_fwd_body<D, METHOD, ABLATE, true, true, TAPE>(a);
   else if (hill2) split_fwd_body<D, METHOD, ABLATE, true, false, TAPE>(a);
@@ -1236,13 +1296,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, HODE_SPL
 
 namespace {
 
+// CUs of the current device (asked once per device; 0 if the runtime does not say, which keeps the 4-wave launch)
+int split_cu_count() {
+  static int cus[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  if (cus[dev] == 0) {
+    int n = 0;
+    cus[dev] = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : -1;
+  }
+  return cus[dev] > 0 ? cus[dev] : 0;
+}
+
 template <int D, bool ABLATE>
 int split_method(const hode_solve_desc* d, const hode::SplitArgs& a, hipStream_t s) {
-  const dim3 grid((d->batch + hode::kSplitPatients - 1) / hode::kSplitPatients), block(256);
+  const dim3 grid((d->batch + hode::kSplitPatients - 1) / hode::kSplitPatients);
   const size_t lds = (size_t)(d->n_times + 3) * sizeof(float);  // the time grid (n_times <= kSplitMaxT)
-#define HODE_SPLIT_FWD(M)                                                                                 \
-  if (a.tape) hipLaunchKernelGGL((hode::split_fwd_kernel<D, M, ABLATE, true>), grid, block, lds, s, a);   \
-  else hipLaunchKernelGGL((hode::split_fwd_kernel<D, M, ABLATE, false>), grid, block, lds, s, a);
+  // the dose wave (HODE_SPLIT_FWD_DOSE): one dose per patient, and no more workgroups than CUs
+  const dim3 fblock(a.K == 1 && (int)grid.x <= split_cu_count() ? hode::kSplitFwdThreads : 256);
+#define HODE_SPLIT_FWD(M)                                                                                \
+  if (a.tape) hipLaunchKernelGGL((hode::split_fwd_kernel<D, M, ABLATE, true>), grid, fblock, lds, s, a);   \
+  else hipLaunchKernelGGL((hode::split_fwd_kernel<D, M, ABLATE, false>), grid, fblock, lds, s, a);
   switch (d->method) {
     case HODE_METHOD_EULER: HODE_SPLIT_FWD(HODE_METHOD_EULER) break;
     case HODE_METHOD_MIDPOINT: HODE_SPLIT_FWD(HODE_METHOD_MIDPOINT) break;

@@ -45,6 +45,25 @@ def classify(op, line):
     return "other"
 
 
+def vmem_counts(instrs):
+    """Loads, stores and atomics to vector memory in `instrs`, and the waits on the vector-memory counter split into
+    vmcnt(0) (everything outstanding, stores included: the counter retires in order) and vmcnt(n > 0)."""
+    n = collections.OrderedDict((k, 0) for k in ("loads", "stores", "atomics", "vmcnt(0)", "vmcnt(n>0)"))
+    for op, s in instrs:
+        if op.startswith(("global_", "buffer_", "flat_", "scratch_")):
+            kind = "loads" if "_load" in op else ("stores" if "_store" in op else ("atomics" if "_atomic" in op else None))
+            if kind:
+                n[kind] += 1
+        elif op.startswith("s_waitcnt"):
+            m = re.search(r"vmcnt\((\d+)\)", s)
+            if m:
+                n["vmcnt(0)" if int(m.group(1)) == 0 else "vmcnt(n>0)"] += 1
+            elif re.fullmatch(r"s_waitcnt\s+(0x)?[0-9a-fA-F]+", s):   # a raw immediate: decode the gfx9 vmcnt field
+                imm = int(s.split()[1], 0)
+                n["vmcnt(0)" if ((imm & 0xF) | ((imm >> 14) & 3) << 4) == 0 else "vmcnt(n>0)"] += 1
+    return list(n.items())
+
+
 def main():
     path, key = sys.argv[1], sys.argv[2]
     lines = open(path).read().split("\n")
@@ -74,6 +93,7 @@ def main():
             continue
         c = collections.Counter(classify(op, s) for op, s in instrs[a:b + 1])
         print("loop %-12s %5d instrs: " % (tgt, b - a + 1) + "  ".join("%s=%d" % kv for kv in c.most_common()))
+        print("     %-12s vector memory: " % "" + "  ".join("%s=%d" % (k, v) for k, v in vmem_counts(instrs[a:b + 1])))
 
 
 if __name__ == "__main__":

@@ -10,7 +10,7 @@ dev = torch.device("cuda:0")
 T = bench.T
 dbg = torch.zeros(6 * (T + 2) + 64 + 8 * (T + 2), dtype=torch.int64, device=dev)
 os.environ["HODE_SPLIT_DBG_PTR"] = hex(dbg.data_ptr())
-dbgf = torch.zeros(4 * T, dtype=torch.int64, device=dev)
+dbgf = torch.zeros(5 * T, dtype=torch.int64, device=dev)   # [5 waves][T]: expert, learned x3, dose wave (if the build has one)
 os.environ["HODE_SPLIT_FWD_DBG_PTR"] = hex(dbgf.data_ptr())
 prob = bench.solver_problem(0)
 plan = bench.build_plan(dev, prob, lanes=0, need_theta=True, tape=True)
@@ -40,10 +40,12 @@ if ph[:, 0].any():   # phase slots: 0 start, 1 reads, 2 adjoint start, 3 = VJP s
     print("   %-52s %5d" % ("whole iteration body (start -> adjoint done)", np.median(ph[:, 7] - ph[:, 0])))
     print("   %-52s %5d" % ("adjoint done -> next iteration start (barrier)", np.median(ph[1:, 0] - ph[:-1, 7])))
 print("forward kernel:")
-sf = dbgf.cpu().numpy().astype(np.int64).reshape(4, T)
+sf = dbgf.cpu().numpy().astype(np.int64).reshape(5, T)
+fnames = names[:4] + ["dose"]
+nf = 5 if sf[4].any() else 4
 ks = np.arange(10, T - 10)
-arr = sf[:, ks]
+arr = sf[:nf, ks]
 last = arr.max(axis=0)
 print("step period: median %d cycles = %.0f ns" % (np.median(np.diff(last)), np.median(np.diff(last)) / 2.4))
-for w in range(4):
-    print("%-10s arrives %5d cycles (median) before the last wave; last in %2d %% of the steps" % (names[w], np.median(last - arr[w]), 100 * np.mean(arr[w] == last)))
+for w in range(nf):
+    print("%-10s arrives %5d cycles (median) before the last wave; last in %2d %% of the steps" % (fnames[w], np.median(last - arr[w]), 100 * np.mean(arr[w] == last)))
